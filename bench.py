@@ -1,6 +1,6 @@
 """bench.py -- DG-Mesh train-step throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,7 +10,14 @@ rasterizer and both MLPs -> (N>1: one flat-bucket RCCL all-reduce) -> Adam updat
 "D-NeRF jumpingjacks, 800x800, ~100k Gaussians, single MI355X, deformation MLP on" (cfg2), synthetic data.
 Frames shard across ranks (weak scaling: every rank renders its own 800x800 frame each step).
 
-Rank 0 prints ONE JSON line.  `value` = frames trained per second over all ranks, inputs resident in HBM.
+Rank 0 prints ONE JSON line.  `value` = frames trained per second over all ranks, inputs resident in HBM; `ms_per_step` =
+milliseconds of one of the K timed steps.  A plain run sets up, primes, warms up, times the K steps and prints the headline
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the workload's `config`, host-side counters of the
+timed region).  `--dump-outputs DIR` then writes what the last timed step computed (rank 0: its loss, rendered image, radii,
+deformed means, screen-space gradient, and the Gaussians and network weights after its Adam update) as DIR/<name>.npy in
+float32, within DUMP_BYTES (a fixed, seeded sample of each array beyond that); the inputs are seeded, so two builds can be
+compared output for output.  Everything below is measured only with `--full` (the stage timers of the per-kernel figures
+then run inside the headline's timed region, as they always did).
 `roofline` describes the DOMINANT hand-written kernel of the step -- chosen at run time as the instrumented kernel
 with the largest (average launch time x launches per step); today the paired backward launch of a 256 -> 256 trunk layer
 (mlp_bwd_pair_kernel: backward data + weight gradient on plane-format activations) -- timed with hipEvents recorded on
@@ -53,6 +60,7 @@ HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8 TB/s
 MFMA_FP32_PEAK_TF = 157.3  # MI355X_MICROARCH.md: dense fp32 MFMA (v_mfma_f32_32x32x2_f32: 64 cycles/SIMD)
 MFMA_16BIT_PEAK_TF = 2500.0  # dense f16 / bf16 MFMA
 STEADY_STEPS = int(os.environ.get("DGM_BENCH_STEADY_STEPS", "200"))
+DUMP_BYTES = 60_000_000  # --dump-outputs: array bytes written in all (cfg2 needs ~38 MB; larger workloads are sampled)
 WORKLOAD = "cfg2"
 TARGETS = "teacher"  # --targets: "teacher" (renders of a perturbed copy of the scene: stationary R) | "noise" (rounds 1-5)
 
@@ -317,6 +325,40 @@ def frac_valu_from_profiles(scene):
     return out
 
 
+def step_outputs(tr, loss, pkg):
+    """What a caller of Trainer.step holds after the step: its return values (loss, render package, the screen-space gradient
+    the densification statistics read) and the parameters its Adam update wrote, as host float32 arrays."""
+    host = lambda t: t.detach().float().cpu().numpy()
+    out = {"loss": host(loss).reshape(1)}
+    for k in ("render", "radii", "means3D"):  # (means3D: the deformed centres, where the renderer returns them)
+        if pkg.get(k) is not None:
+            out[k] = host(pkg[k])
+    vs = pkg.get("viewspace_points")
+    if vs is not None and vs.grad is not None:
+        out["viewspace_points_grad"] = host(vs.grad)
+    for name, p in zip(("xyz", "features_dc", "features_rest", "opacity", "scaling", "rotation"), tr.g.parameters()):
+        out[name] = host(p)
+    nets = [tr.deform, tr.deform_back] + (tr.mesh.networks() if tr.mesh is not None else [])
+    for m in nets:
+        for n, p in m.net.named_parameters():
+            out[f"{m.model_name}.{n}"] = host(p)
+    return out
+
+
+def dump_outputs(out_dir, arrays):
+    """DIR/<name>.npy for every array; when they exceed DUMP_BYTES together, each is replaced by the same fraction of its
+    elements (flattened), drawn with a fixed seed -- the same arrays give the same sample in every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    frac = min(1.0, DUMP_BYTES / total) if total else 1.0
+    for name, a in arrays.items():
+        if frac < 1.0 and a.size > 1:
+            flat = a.reshape(-1)
+            idx = np.sort(np.random.default_rng(0).choice(flat.size, max(1, int(flat.size * frac)), replace=False))
+            a = flat[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -335,6 +377,12 @@ def main():
                          "phase -- four networks on P, DPSR chain, deform_back + appearance on V (BASELINE config 5's 'DPSR mesh step')")
     ap.add_argument("--dpsr-res", type=int, default=288)
     ap.add_argument("--verts", type=int, default=60000)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: stage timers, per-kernel and roofline figures, "
+                         "the steady-state region, the extras (--no-extras), the CPU baseline (--no-cpu-baseline) and, at N > 1, "
+                         "the replica check, the overlapped exchange and the all-reduce on its own")
     args = ap.parse_args()
     global WORKLOAD, TARGETS
     WORKLOAD = args.workload
@@ -397,31 +445,35 @@ def main():
         tr.step(it0 + i)
     RZ = importlib.import_module("dg-mesh_amd.rasterizer")
 
-    def timed(n_steps, first_it):
-        """Barrier + synchronize on both sides, max over ranks; stage timers collected over exactly this region."""
+    def timed(n_steps, first_it, profile=True):
+        """Barrier + synchronize on both sides, max over ranks; with `profile`, stage timers collected over exactly this region."""
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
-        L.lib().dgm_set_profiling_sampling(8)  # bracket every 8th launch of a stage: ~12 event pairs per step instead of ~90
-        L.lib().dgm_set_profiling(2)
+        if profile:
+            L.lib().dgm_set_profiling_sampling(8)  # bracket every 8th launch of a stage: ~12 event pairs per step instead of ~90
+            L.lib().dgm_set_profiling(2)
         torch.cuda.synchronize()
         RZ.FORWARD_CALL_SECONDS = 0.0
         RZ.SETTLE_WAIT_SECONDS = 0.0
         t0 = time.perf_counter()
-        pk = None
+        pk = loss = None
         for i in range(n_steps):
             pk = None  # (let go of the previous step's render package BEFORE the next step allocates its own: holding it across
             #            the call kept one extra set of frame tensors alive and cost the region one device allocation)
-            _, pk = tr.step(first_it + i)
+            loss, pk = tr.step(first_it + i)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        st = L.collect_stage_ms()
-        L.lib().dgm_set_profiling(0)
+        st = {}
+        if profile:
+            st = L.collect_stage_ms()
+            L.lib().dgm_set_profiling(0)
         blocked = RZ.FORWARD_CALL_SECONDS
         timed.settle_wait = RZ.SETTLE_WAIT_SECONDS
+        timed.loss = loss
         if world > 1:
             tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -432,15 +484,59 @@ def main():
         """Mean device time of the gradient exchange section of a step (pack, all-reduce(s), wait) on the compute stream."""
         return sum(a.elapsed_time(b) for a, b in events) / max(len(events), 1)
 
-    if world > 1:
+    if world > 1 and args.full:
         tr.exchange_events = []
     dev_allocs0 = torch.cuda.memory_stats(dev).get("num_device_alloc", 0)
     redos0 = RZ.OVERFLOW_REDOS + RZ.UNIT_REDOS
-    elapsed, stages, blocked_s, pkg = timed(args.steps, it0 + args.warmup)
+    elapsed, stages, blocked_s, pkg = timed(args.steps, it0 + args.warmup, profile=args.full)
     settle_s, redos = timed.settle_wait, RZ.OVERFLOW_REDOS + RZ.UNIT_REDOS - redos0
     # hipMalloc calls of torch's caching allocator inside the timed region: 0 at steady state; a scene whose R keeps setting new
     # maxima (cfg4 under the random targets) pays one multi-GB allocation per new size of the binning buffer
     dev_allocs = torch.cuda.memory_stats(dev).get("num_device_alloc", 0) - dev_allocs0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(tr, timed.loss, pkg))
+    gemm_mode = L.lib().dgm_mlp_set_gemm(-1) if mlp_impl == "hip" else -1  # (-1: query, mode unchanged)
+
+    def headline(n_inst, live_rows):
+        """The result line's fields that need nothing beyond the timed region (rank 0)."""
+        R = int((pkg["radii"] > 0).sum().item())  # visible Gaussians of the last frame (informational)
+        return {
+            "metric": ("train-step iters/sec (800x800, ~100k Gaussians)" if WORKLOAD == "cfg2"
+                       else f"train-step iters/sec ({WORKLOAD}: {W}x{H}, P={P}; informational, the metric is quoted on cfg2)"),
+            "value": args.steps * world / elapsed,
+            "unit": "it/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": ("f32 (f16x3p split products, fp32 accumulate)" if mlp_impl == "hip" and gemm_mode >= 3 else
+                                          "f32 (native fp32 MFMA)" if gemm_mode == 1 else "f32"), "data": "synthetic",
+            "phase": ("dynamic Gaussian splatting (deform + deform_back)" if args.phase == "gs" else
+                      f"mesh co-training: deform, deform_normal, deform_back, deform_back_normal on P + DPSR {args.dpsr_res}^3 (splat, "
+                      f"spectral solve, read-back, adjoints) + deform_back and appearance on V={args.verts} vertices; DPSR step included, "
+                      "DiffMC / nvdiffrast replaced by a probe of phi (third-party, out of scope)"),
+            "config": {"workload": ("D-NeRF jumpingjacks-like cfg2: 800x800, P=100000 Gaussians, deformation MLP on "
+                                    "(deform + deform_back, is_blender), 1 frame per rank per step, fixed P (no densification "
+                                    "inside the timed region); output heads of both networks scaled x0.01 so that the deformation "
+                                    "field is small as after convergence (default init triples every splat's extent)") if WORKLOAD == "cfg2" else
+                                   f"{WORKLOAD} of BASELINE.json: {W}x{H}, P={P} Gaussians, deformation MLP on, 1 frame per rank per "
+                                   "step, fixed P",
+                       "P": P, "W": W, "H": H, "num_rendered": n_inst, "live_rows": live_rows, "visible": R, "mlp_impl": mlp_impl,
+                       "parallelism": f"dp{world} (frame-parallel, flat-bucket all-reduce {tr.grad_bytes() / 1e6:.1f} MB)"},
+            # host side: time inside the rasterizer forward call (synchronous protocol: its R read-back is the step's only sync;
+            # DGM_SYNC_FREE=1: the call only enqueues and {R, flags} are looked at after the backward is enqueued -- `settle_wait`)
+            "host_ms_per_step": {"blocked_on_gpu": round(1e3 * blocked_s / args.steps, 3),
+                                 "busy": round(1e3 * (elapsed - blocked_s) / args.steps, 3),
+                                 "device_allocations_in_timed_region": int(dev_allocs),
+                                 "sync_free_forward": bool(RZ.SYNC_FREE), "settle_wait": round(1e3 * settle_s / args.steps, 3),
+                                 "frames_redone_for_capacity": int(redos)},
+            "rccl_world_size": dist.get_world_size() if world > 1 else 1,
+        }
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(int(RZ.LAST_NUM_RENDERED), None)), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     dp = None
     if world > 1:
         # Self-verification of the data-parallel run: every rank must hold bit-identical parameters and Adam moments after the
@@ -560,8 +656,6 @@ def main():
             trained = {"error": str(ex)}
 
     if rank == 0:
-        # R of the last frame (all frames of the synthetic orbit are statistically alike)
-        R = int((pkg["radii"] > 0).sum().item())  # visible Gaussians (informational)
         n_inst = n_inst_timed  # tile instances R
         bwd_ms, bwd_n = stages.get("render_bwd", (0.0, 0))
         alg_bytes = 40.0 * n_inst + 20.0 * W * H + 36.0 * P  # render bwd per frame
@@ -593,7 +687,6 @@ def main():
                 return None, None, f"profiles/{name} refused: {why}"
             return float(pmc["fetch_bytes"]) + float(pmc["write_bytes"]), name, pmc["commit"]
 
-        gemm_mode = L.lib().dgm_mlp_set_gemm(-1) if mlp_impl == "hip" else -1  # (-1: query, mode unchanged)
         mfma_per_product = 3.0  # f16x3 / f16x3p: 3 MFMAs per fp32 product on the f16 pipe
         layer_flops = 2.0 * P * 256 * 256                       # one 256 -> 256 layer over N = P rows
         layer_bytes = 2.0 * P * 256 * 4 + P * 32 + 256 * 256 * 4  # A in + C out (fp32) + ReLU mask bits + the weights once
@@ -676,26 +769,8 @@ def main():
                                                              "against the 8 TB/s of the data sheet"}
             del src_t, dst_t
         rb_traffic, rb_src, _ = pmc_traffic("r06_pmc_render_bwd4.json", "render_bwd4_kernel")
-        out = {
-            "metric": ("train-step iters/sec (800x800, ~100k Gaussians)" if WORKLOAD == "cfg2"
-                       else f"train-step iters/sec ({WORKLOAD}: {W}x{H}, P={P}; informational, the metric is quoted on cfg2)"),
-            "value": args.steps * world / elapsed,
-            "unit": "it/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": ("f32 (f16x3p split products, fp32 accumulate)" if mlp_impl == "hip" and gemm_mode >= 3 else
-                                          "f32 (native fp32 MFMA)" if gemm_mode == 1 else "f32"), "data": "synthetic",
-            "phase": ("dynamic Gaussian splatting (deform + deform_back)" if args.phase == "gs" else
-                      f"mesh co-training: deform, deform_normal, deform_back, deform_back_normal on P + DPSR {args.dpsr_res}^3 (splat, "
-                      f"spectral solve, read-back, adjoints) + deform_back and appearance on V={args.verts} vertices; DPSR step included, "
-                      "DiffMC / nvdiffrast replaced by a probe of phi (third-party, out of scope)"),
-            "config": {"workload": ("D-NeRF jumpingjacks-like cfg2: 800x800, P=100000 Gaussians, deformation MLP on "
-                                    "(deform + deform_back, is_blender), 1 frame per rank per step, fixed P (no densification "
-                                    "inside the timed region); output heads of both networks scaled x0.01 so that the deformation "
-                                    "field is small as after convergence (default init triples every splat's extent)") if WORKLOAD == "cfg2" else
-                                   f"{WORKLOAD} of BASELINE.json: {W}x{H}, P={P} Gaussians, deformation MLP on, 1 frame per rank per "
-                                   "step, fixed P",
-                       "P": P, "W": W, "H": H, "num_rendered": n_inst, "live_rows": n_live_timed, "visible": R, "mlp_impl": mlp_impl,
-                       "parallelism": f"dp{world} (frame-parallel, flat-bucket all-reduce {tr.grad_bytes() / 1e6:.1f} MB)"},
+        out = headline(n_inst, n_live_timed)
+        out.update({
             "roofline": roof,
             # the rasterizer backward, graded against HBM by BASELINE.json's north_star (VALU-bound in practice:
             # profiles/*pmc_sq*.json)
@@ -705,15 +780,7 @@ def main():
                                     "launches": bwd_n},
             "kernels": kernels,
             "stages_ms": {k: round(v[0], 4) for k, v in stages.items()},
-            # host side: time inside the rasterizer forward call (synchronous protocol: its R read-back is the step's only sync;
-            # DGM_SYNC_FREE=1: the call only enqueues and {R, flags} are looked at after the backward is enqueued -- `settle_wait`)
-            "host_ms_per_step": {"blocked_on_gpu": round(1e3 * blocked_s / args.steps, 3),
-                                 "busy": round(1e3 * (elapsed - blocked_s) / args.steps, 3),
-                                 "device_allocations_in_timed_region": int(dev_allocs),
-                                 "sync_free_forward": bool(RZ.SYNC_FREE), "settle_wait": round(1e3 * settle_s / args.steps, 3),
-                                 "frames_redone_for_capacity": int(redos)},
-        }
-        out["rccl_world_size"] = dist.get_world_size() if world > 1 else 1
+        })
         if dp is not None:
             out["replicas_identical"] = dp["replicas_identical"]
             out["data_parallel"] = dp

@@ -85,7 +85,7 @@ def test_bench_gpus_flag_launches_its_own_ranks(workload, steps, sync_free):
     else:
         env.pop("DGM_SYNC_FREE", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", str(steps), "--warmup", "2", "--workload",
-                          workload, "--no-cpu-baseline", "--no-extras"], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                          workload, "--full", "--no-cpu-baseline", "--no-extras"], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
                          text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
