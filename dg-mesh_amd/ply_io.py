@@ -129,3 +129,57 @@ def load_gaussians(path, max_sh_degree=3):
     if "gaussian_scale" in ply:
         out["gaussian_scale"] = np.float32(ply["gaussian_scale"]["gaussian_scale"][0])
     return out
+
+
+# ---- triangle meshes (export_mesh, R/scene/gaussian_model_dpsr_dynamic_anchor.py:831-856) ----------------------------------------
+# binary_little_endian: `element vertex V` with float x y z, `element face F` with `property list uchar int vertex_indices`, the
+# layout MeshLab, trimesh and Open3D read.  (A separate pair from write_ply / read_ply: the checkpoint format has no list
+# properties and read_ply keeps refusing them.)
+def write_mesh_ply(path, verts, faces):
+    """verts (V, 3) float, faces (F, 3) int (numpy arrays or tensors on any device)."""
+    as_np = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+    v = np.ascontiguousarray(as_np(verts), dtype="<f4").reshape(-1, 3)
+    f = np.asarray(as_np(faces)).reshape(-1, 3)
+    if f.size and (f.min() < 0 or f.max() >= len(v)):
+        raise ValueError("write_mesh_ply: face index out of range")
+    rec = np.empty(len(f), dtype=[("n", "u1"), ("idx", "<i4", (3,))])
+    rec["n"], rec["idx"] = 3, f
+    head = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}", "property float x", "property float y",
+            "property float z", f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(head) + "\n").encode("ascii"))
+        fh.write(v.tobytes())
+        fh.write(rec.tobytes())
+
+
+def read_mesh_ply(path):
+    """-> verts (V, 3) float32, faces (F, 3) int32 of a binary little-endian triangle-mesh PLY as write_mesh_ply writes it."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.index(b"\n", data.index(b"end_header")) + 1
+    lines = [ln.split() for ln in data[:end].decode("ascii").splitlines()]
+    if lines[0] != ["ply"] or ["format", "binary_little_endian", "1.0"] not in lines:
+        raise ValueError(f"{path}: not a binary little-endian PLY")
+    elems = []
+    for tok in lines:
+        if tok and tok[0] == "element":
+            elems.append((tok[1], int(tok[2]), []))
+        elif tok and tok[0] == "property":
+            elems[-1][2].append(tok[1:])
+    by = {name: (n, props) for name, n, props in elems}
+    nv, vprops = by["vertex"]
+    if [p[-1] for p in vprops][:3] != ["x", "y", "z"] or any(p[0] == "list" for p in vprops):
+        raise ValueError(f"{path}: vertex element must start with x y z scalars")
+    vdt = np.dtype([(p[1], "<" + _PLY_TYPES[p[0]]) for p in vprops])
+    off = end
+    v = np.frombuffer(data, dtype=vdt, count=nv, offset=off)
+    off += nv * vdt.itemsize
+    verts = np.stack([v["x"], v["y"], v["z"]], 1).astype(np.float32)
+    nf, fprops = by.get("face", (0, []))
+    if nf and fprops != [["list", "uchar", "int", "vertex_indices"]] and fprops != [["list", "uchar", "int", "vertex_index"]]:
+        raise ValueError(f"{path}: face element must be `property list uchar int vertex_indices`")
+    f = np.frombuffer(data, dtype=[("n", "u1"), ("idx", "<i4", (3,))], count=nf, offset=off)
+    if nf and (f["n"] != 3).any():
+        raise ValueError(f"{path}: only triangles are supported")
+    return verts, f["idx"].astype(np.int32).reshape(-1, 3)

@@ -9,11 +9,16 @@ Mesh co-training phase (`mesh=MeshPhase(...)`, iteration >= dpsr_iter; R/train.p
 R/utils/renderer.py:150-183): the two normal networks (deform_normal, deform_back_normal: DeformNetworkNormalSep on the P
 Gaussians, cycle loss / 4), the DPSR chain on the deformed points and normals (normalise to the unit cube -> trilinear splat ->
 spectral Poisson solve -> sign fix -> minus density threshold), deform_back + appearance on the V mesh vertices, six Adam
-steps (+ the density threshold).  What sits between phi and the image losses in the reference -- DiffMC marching cubes and
-nvdiffrast, third-party packages outside /root/reference (parity unpinned) -- is NOT rebuilt; in its
-place phi is read back trilinearly (grid_interp, with its adjoint) at V fixed probe points and those probes act as the mesh
-vertices, with L1 losses against fixed targets standing in for the mask / mesh-image losses.  Every kernel chain of the phase
-that the reference owns therefore runs and is differentiated; the numbers of the stand-in losses mean nothing.
+steps (+ the density threshold).  Between phi and the image losses the reference runs DiffMC marching cubes and nvdiffrast,
+third-party packages outside the reference (parity unpinned).  The mesh comes from one of two sources:
+  * mesh_source="probes" (default): phi is read back trilinearly (grid_interp, with its adjoint) at V fixed probe points and those
+    probes act as the mesh vertices;
+  * mesh_source="diffmc": the mesh is extracted by this project's marching cubes (marching_cubes.DiffMC, csrc/marching_cubes.hip)
+    at isovalue 0 and mapped to world space like R/utils/renderer.py:171-174; deform_back + appearance run on its vertices and the
+    Laplacian regulariser on its faces (R/train.py:278-285), so those terms reach the density threshold, the normals and the
+    positions through DiffMC and DPSR.
+nvdiffrast is not rebuilt in either: L1 losses against fixed targets stand in for the mask / mesh-image losses, and their numbers
+mean nothing.
 Host synchronisations of the reference's loop that do not change results are dropped
 (torch.cuda.empty_cache() every iteration, R/train.py:130; get_psnr's .item(), :315).
 
@@ -120,8 +125,15 @@ class MeshPhase:
     `center`, `scale` given here initialise them (R/train.py: normal_initialization sets init_density_threshold)."""
 
     def __init__(self, deform_normal, deform_back_normal, appearance, dpsr=None, n_verts=20000, density_thres=None,
-                 center=None, scale=None, seed=0, device="cuda", stand_in_weight=1e-6):
+                 center=None, scale=None, seed=0, device="cuda", stand_in_weight=1e-6, mesh_source="probes",
+                 laplacian_loss_weight=1.0):
+        if mesh_source not in ("probes", "diffmc"):
+            raise ValueError(f"MeshPhase: mesh_source must be 'probes' or 'diffmc', got {mesh_source!r}")
         self.stand_in_weight = stand_in_weight
+        self.mesh_source, self.laplacian_loss_weight = mesh_source, laplacian_loss_weight
+        from .marching_cubes import DiffMC
+        self.diffmc = DiffMC(dtype=torch.float32)  # (stateless; also used by extract_mesh)
+        self.last_mesh = None  # (world-space verts detached, faces) of the latest "diffmc" step
         self.deform_normal, self.deform_back_normal, self.appearance, self.dpsr = deform_normal, deform_back_normal, appearance, dpsr
         dev = torch.device(device)
         gen = torch.Generator().manual_seed(4242 + seed)
@@ -148,6 +160,40 @@ class MeshPhase:
 
     def networks(self):
         return [self.deform_normal, self.deform_back_normal, self.appearance]
+
+    def psr(self, g, deform, deform_normal, freeze_pos=False):
+        """phi of the deformed Gaussians, signed and shifted by the density threshold (R/utils/renderer.py:150-168): (R, R, R), the
+        surface at 0.  deform / deform_normal: the networks' outputs at the Gaussians (d_xyz (P, 3), d_normal (P, 3)) or None;
+        freeze_pos: no gradient to the positions (the normal warm-up)."""
+        pts = g.get_xyz.detach() + deform.detach() if freeze_pos and deform is not None else (
+            g.get_xyz + deform if deform is not None else g.get_xyz)
+        pts = ((pts - g.gaussian_center) / g.gaussian_scale) / 2.0 + 0.5
+        pts = torch.clamp(pts, 1e-6, 1 - 1e-6)
+        normals = g.get_normal + deform_normal if deform_normal is not None else g.get_normal
+        psr = self.dpsr(pts.unsqueeze(0), normals.unsqueeze(0))
+        sign = torch.where(psr[0, 0, 0, 0].detach() < 0, -1.0, 1.0)                       # (no host read-back of the sign)
+        return (psr * sign - g.density_thres_param)[0]
+
+    def surface(self, g, psr):
+        """DiffMC at isovalue 0, mapped from the unit cube to world space (R/utils/renderer.py:171-174): verts (V, 3), faces (F, 3) int32."""
+        verts, faces = self.diffmc(psr, deform=None, isovalue=0.0)
+        verts = verts * 2.0 - 1.0
+        return verts * g.gaussian_scale + g.gaussian_center, faces
+
+    @torch.no_grad()
+    def extract_mesh(self, g, deform=None, deform_normal=None, t=None):
+        """export_mesh (R/scene/gaussian_model_dpsr_dynamic_anchor.py:831-856): world-space (verts, faces) of the surface at time t.
+        deform / deform_normal: DeformModel-like objects with .step(xyz, t) (the first output is used), or None for the canonical
+        Gaussians; t: a scalar time (float or tensor).  Write the result with ply_io.write_mesh_ply."""
+        if self.dpsr is None:
+            raise RuntimeError("MeshPhase.extract_mesh needs the DPSR module")
+        xyz = g.get_xyz
+        tt = None if t is None else torch.as_tensor(t, dtype=torch.float32, device=xyz.device).reshape(1, 1).expand(xyz.shape[0], -1)
+        d_xyz = deform.step(xyz.detach(), tt)[0] if deform is not None else None
+        d_normal = deform_normal.step(xyz.detach(), tt) if deform_normal is not None else None
+        if isinstance(d_normal, (tuple, list)):
+            d_normal = d_normal[0]
+        return self.surface(g, self.psr(g, d_xyz, d_normal))
 
 
 class Trainer:
@@ -402,16 +448,13 @@ class Trainer:
         # R/utils/renderer.py:150-170: points of the deformed Gaussians in the unit cube, their normals, phi, sign, threshold
         dx = delta[:, :3] if delta is not None else d_xyz
         freeze_pos = iteration < opt.dpsr_iter + opt.normal_warm_up
-        pts = (xyz_d + dx.detach()) if freeze_pos else (g.get_xyz + dx)
-        pts = ((pts - g.gaussian_center) / g.gaussian_scale) / 2.0 + 0.5
-        pts = torch.clamp(pts, 1e-6, 1 - 1e-6)
-        normals = g.get_normal + d_normal if d_normal is not None else g.get_normal
-        psr = ms.dpsr(pts.unsqueeze(0), normals.unsqueeze(0))
-        sign = torch.where(psr[0, 0, 0, 0].detach() < 0, -1.0, 1.0)                       # (no host read-back of the sign)
-        psr = psr * sign - g.density_thres_param
+        psr = ms.psr(g, dx, d_normal, freeze_pos=freeze_pos)
+        if ms.mesh_source == "diffmc":
+            self.diffmc_terms(cam, iteration, losses, psr)
+            return
         # stand-in for DiffMC -> nvdiffrast: phi at the V probe points; the probes act as the mesh vertices
         from .dpsr import grid_interp
-        phi_v = grid_interp(psr.unsqueeze(-1), ms.probes.unsqueeze(0))[0, :, 0]
+        phi_v = grid_interp(psr[None, ..., None], ms.probes.unsqueeze(0))[0, :, 0]
         # (stand-in losses carry a tiny weight: they exist to drive the chain's backward, not to shape the scene)
         losses["mask_loss"] = S.l1_loss(phi_v, ms.phi_target) * 100 * opt.mask_loss_weight * ms.stand_in_weight
         V = ms.verts.shape[0]
@@ -419,6 +462,28 @@ class Trainer:
         back_v = self.deform_back.step(ms.verts, t_v)[0]                                  # R/utils/renderer.py:179-181
         vtx_color = ms.appearance.step(ms.verts + back_v, t_v)
         losses["mesh_img_loss"] = S.l1_loss(vtx_color, ms.color_target) * opt.mesh_img_loss_weight * (1e3 * ms.stand_in_weight)
+
+    def diffmc_terms(self, cam, iteration, losses, psr):
+        """mesh_source="diffmc": the mesh of phi (R/utils/renderer.py:171-181), the vertex colours and the Laplacian regulariser
+        (R/train.py:278-285, with its (1 - iteration / iterations) decay); the mask / mesh-image stand-ins are fixed functions of
+        the vertex positions (V changes every step)."""
+        from .dpsr import laplace_regularizer_const
+        opt, ms = self.opt, self.mesh
+        verts, faces = ms.surface(self.g, psr)
+        ms.last_mesh = (verts.detach(), faces)
+        V = verts.shape[0]
+        if V == 0:  # (an empty surface: nothing for the vertex networks or the regulariser to see)
+            return
+        t_v = cam.fid.reshape(1, 1).expand(V, -1)
+        back_v = self.deform_back.step(verts.detach(), t_v)[0]                            # R/utils/renderer.py:179-181
+        vtx_color = ms.appearance.step(verts + back_v, t_v)
+        u = (verts - self.g.gaussian_center) / self.g.gaussian_scale                      # [-1, 1]
+        radius = u.norm(dim=1)
+        losses["mask_loss"] = S.l1_loss(radius, torch.full_like(radius, 0.5)) * 100 * opt.mask_loss_weight * ms.stand_in_weight
+        color_target = 0.5 + 0.5 * torch.sin(3.0 * u.detach())
+        losses["mesh_img_loss"] = S.l1_loss(vtx_color, color_target) * opt.mesh_img_loss_weight * (1e3 * ms.stand_in_weight)
+        t_iter = iteration / opt.iterations
+        losses["laplacian_loss"] = laplace_regularizer_const(verts, faces) * (1000 * ms.laplacian_loss_weight) * (1 - t_iter)
 
     def step(self, iteration):
         g = self.g

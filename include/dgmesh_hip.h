@@ -53,7 +53,8 @@ extern "C" {
  *      gradient row of an instance itself); dgm_laplace_* added.  Entry points' signatures are unchanged from 3.
  *   5: dgm_rasterize_forward_capacity added (a forward that never waits for the device); dgm_se3_* added (6-DoF heads);
  *      dgm_mlp_set_gemm knows modes 4 and 5.
- *      Every entry point of 4 is unchanged. */
+ *      Every entry point of 4 is unchanged.
+ *      Later additions that leave every existing entry point and layout unchanged keep the number: dgm_mc_* (marching cubes). */
 #define DGM_ABI_VERSION 5
 
 /* Allocator callback: must return a device pointer to at least `bytes` bytes (128-byte aligned),
@@ -416,6 +417,29 @@ size_t dgm_opacity_field_scratch_bytes(int P);
 int dgm_opacity_field(int P, const float* xyz, const float* rotations, const float* scalings, const float* opacities,
                       float opacity_threshold, int res, int num_blocks, float margin, const float* coords, char* scratch,
                       float* occ, void* stream);
+
+/* ---- marching cubes (csrc/marching_cubes.hip) -------------------------------------------------------------------------------
+ * Replaces diso.DiffMC (the reference's mesh extraction, dgmesh/utils/renderer.py:171).  grid (X, Y, Z) fp32 row-major [x][y][z],
+ * every dimension >= 2 and 5 X Y Z < 2^31; point (i, j, k) sits at (i, j, k) (+ deform[i][j][k][0..2] when deform != NULL).
+ * A point is inside iff f < iso (NaN: outside); edge a->b is crossed iff inside(a) != inside(b); its vertex is
+ * p_a + t (p_b - p_a), t = (iso - fa) / (fb - fa), divided by (dim - 1) per axis when normalize != 0.
+ * Vertices: one per crossed edge, ordered by the owning point's linear index (i Y + j) Z + k (a point owns its +x, +y, +z edges),
+ * then by axis.  Faces: int32 vertex triples ordered by cell linear index (i (Y-1) + j) (Z-1) + k, then by the case table
+ * (csrc/mc_tables.hpp, generated by tools/gen_mc_tables.py), wound so that (v1 - v0) x (v2 - v0) points towards f >= iso.
+ * All orders come from prefix sums: output is identical run to run.
+ *   dgm_mc_scratch_bytes: caller-owned device scratch for one extraction (0 for invalid dimensions); count, emit and backward of
+ *                         one extraction use the same scratch, and the grid must not change between them.
+ *   dgm_mc_count   : classifies the cells and writes counts[0] = V, counts[1] = F (device ints).  The caller reads them back
+ *                    (the extraction's one host synchronisation) and sizes the outputs.
+ *   dgm_mc_emit    : writes verts (V, 3) fp32 and faces (F, 3) int32 (V, F: the counts; NULL allowed where a count is 0).
+ *   dgm_mc_backward: dgrid (X, Y, Z) and, when deform != NULL, ddeform (X, Y, Z, 3) = the gradients of sum(dverts * verts),
+ *                    both overwritten; a gather without atomics (bit-reproducible). */
+size_t dgm_mc_scratch_bytes(int X, int Y, int Z);
+int dgm_mc_count(int X, int Y, int Z, const float* grid, float iso, char* scratch, int* counts, void* stream);
+int dgm_mc_emit(int X, int Y, int Z, const float* grid, const float* deform, float iso, int normalize, char* scratch, int V, int F,
+                float* verts, int* faces, void* stream);
+int dgm_mc_backward(int X, int Y, int Z, const float* grid, const float* deform, float iso, int normalize, const char* scratch, int V,
+                    const float* dverts, float* dgrid, float* ddeform, void* stream);
 
 #ifdef __cplusplus
 }
