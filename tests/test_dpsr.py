@@ -107,3 +107,68 @@ def test_laplace_regularizer_hip_kernels():
     err = (vt.grad.double() - v64.grad).abs().max().item() / v64.grad.abs().max().item()
     assert err < 1e-5, err
     assert float(vt.grad[-5:].abs().max()) == 0.0
+
+
+# ---- the Laplacian kernels at the edges of their input -----------------------------------------------------------------------------
+def _laplace_vs_fp64(name, v, faces, tol=1e-5):
+    """HIP loss and gradient against _laplace_regularizer_torch in float64 on the same mesh.  1e-5: a vertex of valence m sums
+    2 m fp32 terms per component by atomics, <= (2 m + 4) u of their absolute sum, ~1e-6 at the valences (<= 15) of a
+    triangulated surface; the normalisation, the square and the block sums add a few u more."""
+    D = pkg("dpsr")
+    vt = torch.tensor(v, dtype=torch.float32, device="cuda", requires_grad=True)
+    ft = torch.as_tensor(faces, device="cuda").to(torch.int64).reshape(-1, 3)
+    loss = D.laplace_regularizer_const(vt, ft)
+    (g,) = torch.autograd.grad(loss * 3.0, vt)
+    v64 = vt.detach().double().requires_grad_(True)
+    want = D._laplace_regularizer_torch(v64, ft)
+    (g64,) = torch.autograd.grad(want * 3.0, v64)
+    lw, gm = float(want.detach()), float(g64.abs().max())
+    if lw == 0.0:  # nothing to normalise by: exactly zero on both sides
+        assert float(loss.detach()) == 0.0 and float(g.abs().max()) == 0.0 and gm == 0.0
+        print(f"laplace {name}: loss and gradient exactly 0")
+        return
+    el = abs(float(loss.detach()) - lw) / abs(lw)
+    eg = float((g.double() - g64).abs().max()) / gm
+    print(f"laplace {name}: loss err {el:.3e} rel, grad err {eg:.3e} of max, bound {tol:.3e} (V={len(v)}, F={ft.shape[0]})")
+    assert el <= tol and eg <= tol
+
+
+@pytest.mark.gpu
+def test_laplace_kernels_on_the_diffmc_meshes_at_scale():
+    """DiffMC's meshes: the 288^3 DPSR grid of the reference configs and a checkerboard (4 triangles per cell, ~4.4 M faces)."""
+    import test_marching_cubes as TM
+    M = pkg("marching_cubes")
+    for name, grid in (("dpsr 288^3", TM.dpsr_phi_288()), ("checkerboard 104^3",
+                                                          torch.tensor(TM.checkerboard((104, 104, 104), 3), device="cuda"))):
+        v, f = M.DiffMC()(grid)
+        assert f.shape[0] > 100000
+        _laplace_vs_fp64(name, v.cpu().numpy(), f.cpu().numpy())
+
+
+@pytest.mark.gpu
+def test_laplace_kernels_on_degenerate_meshes():
+    rng = np.random.RandomState(4)
+    v = rng.randn(1000, 3)
+    f = rng.randint(0, 1000, (3000, 3))
+    i = rng.randint(0, 1000, 400)
+    j = rng.randint(0, 1000, 400)
+    rep = np.concatenate([np.stack([i[:200], i[:200], j[:200]], 1), np.stack([j[200:], i[200:], i[200:]], 1),
+                          np.stack([i, i, i], 1)], 0)  # (i, i, j), (j, i, i) and (i, i, i)
+    _laplace_vs_fp64("repeated indices", v, np.concatenate([f, rep], 0))
+    _laplace_vs_fp64("only repeated indices", v, rep)
+    _laplace_vs_fp64("F = 0", v, np.zeros((0, 3), np.int64))
+    _laplace_vs_fp64("V = 1, F = 0", v[:1], np.zeros((0, 3), np.int64))
+    _laplace_vs_fp64("V = 1, face (0, 0, 0)", v[:1], np.zeros((1, 3), np.int64))
+
+
+@pytest.mark.gpu
+def test_laplace_kernels_on_a_100k_fan():
+    """100 k faces on one hub vertex: 200 k atomic terms per component meet at one address.  The hub's sum carries the
+    atomic-order bound (2 m + 4) u of its absolute sum with m = 100 k (1.2e-2); the hub sits off the rim's centre so that the
+    sum does not cancel and its absolute sum stays within a small factor of the result."""
+    n = 100000
+    th = np.linspace(0, 2 * np.pi, n + 1)
+    rim = np.stack([np.cos(th), np.sin(th), 0.2 * np.sin(7 * th)], 1)
+    v = np.concatenate([[[0.6, 0.3, 0.5]], rim], 0)
+    f = np.stack([np.zeros(n, np.int64), np.arange(1, n + 1), np.arange(2, n + 2)], 1)
+    _laplace_vs_fp64("fan of 100k faces", v, f, tol=(2 * n + 4) * 2.0 ** -24)

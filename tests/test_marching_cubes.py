@@ -2,7 +2,9 @@
 tools/gen_mc_tables.py).  diso is not vendored, so there is no third-party output to compare with: the CPU tests check that the
 table is what its generator writes and that the restatement of the conventions (tests/_mc_ref.py) produces closed, consistently
 oriented meshes; the GPU tests check the kernels against that restatement exactly, the meshes geometrically, the adjoint against
-the analytic one and central differences, and the mesh phase of the trainer on DiffMC's mesh."""
+the analytic one and central differences, and the mesh phase of the trainer on DiffMC's mesh.  At scale: bit-exact on grids
+around the block scan's one-segment-per-thread limit (NB = 1024, 1025, 1055, 1099) and on the 288^3 DPSR grid, whose backward
+is checked there too."""
 import math
 import os
 import subprocess
@@ -305,3 +307,80 @@ def test_density_threshold_gradient_flows_through_diffmc():
     DP.laplace_regularizer_const(verts, faces).backward()
     for p in (g.density_thres_param, g._normal, g._xyz):
         assert p.grad is not None and bool(torch.isfinite(p.grad).all()) and float(p.grad.abs().max()) > 0
+
+
+# ---- at scale: the block scan past one segment per thread, the 288^3 DPSR grid of the reference configs --------------------------
+def _bit_exact(grid, iso=0.0, deform=None, normalize=True):
+    """vertices bit-equal and faces equal to the restatement -> (verts, faces, restatement record)."""
+    v, f = _gpu(grid, iso, deform, normalize)
+    rv, rf, rec = R.marching_cubes(grid, iso, deform, normalize)
+    assert f.shape == rf.shape and np.array_equal(f, rf)
+    assert v.shape == rv.shape and np.array_equal(v.view(np.int32), rv.view(np.int32)), float(np.abs(v - rv).max())
+    print(f"grid {grid.shape}: {len(rv)} vertices, {len(rf)} faces bit-equal")
+    return v, f, rec
+
+
+def _scan_blocks(shape):
+    """NB of dgm_mc_count: one block total per 1024 points, scanned by mc_scan_kernel's 1024 threads, ceil(NB / 1024) each."""
+    return -(-int(np.prod(shape)) // 1024)
+
+
+def checkerboard(shape, seed):
+    """Alternating signs: every cell is the two-tetrahedra case, 4 triangles, every edge crossed -- the densest mesh."""
+    i, j, k = np.meshgrid(*(np.arange(s) for s in shape), indexing="ij")
+    mag = np.random.RandomState(seed).uniform(0.3, 1.0, shape)
+    return (np.where((i + j + k) % 2 == 0, -1.0, 1.0) * mag).astype(np.float32)
+
+
+def dpsr_phi_288(sig=3.0):
+    """The indicator grid of the reference configs' DPSR (grid_res 288, dpsr_sig 3.0) on a noisy oriented sphere, on the device."""
+    import _dpsr_ref
+    D = pkg("dpsr")
+    Vn, Nn = _dpsr_ref.noisy_sphere(100000, 288)
+    V, N = torch.tensor(Vn, device="cuda"), torch.tensor(Nn, device="cuda")
+    return D.DPSR(res=(288, 288, 288), sig=sig)(V.unsqueeze(0), N.unsqueeze(0))[0]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape,nb", [((64, 128, 128), 1024), ((2, 2, 262145), 1025), ((262145, 2, 2), 1025),
+                                      ((2, 600, 900), 1055)])
+def test_gpu_bit_exact_around_one_scan_segment_per_thread(shape, nb):
+    """NB = 1024 gives every scan thread one block; NB = 1025 and 1055 give seg = 2 with a ragged last thread, so a rounded-down
+    segment would leave the last blocks' offsets unwritten."""
+    assert _scan_blocks(shape) == nb
+    _, f, _ = _bit_exact(_noise(shape, nb), 0.0)
+    assert len(f) > 0
+
+
+@pytest.mark.gpu
+def test_gpu_bit_exact_on_a_checkerboard_past_one_segment():
+    shape = (104, 104, 104)
+    assert _scan_blocks(shape) == 1099
+    v, f, _ = _bit_exact(checkerboard(shape, 3), 0.0)
+    assert len(f) == 4 * 103 ** 3
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("with_deform", [False, True])
+def test_gpu_on_the_dpsr_grid_at_288(with_deform):
+    """The GPU's DPSR phi at 288^3 fed to both sides: forward bit-exact, backward within 1e-6 of max of the analytic adjoint
+    (per grid point <= 6 incident edges of 3 terms, each a few roundings: ~30 u = 1.8e-6 of the largest term; the terms of one
+    point rarely cancel to below half of the max) and bit-identical run to run."""
+    grid = dpsr_phi_288().cpu().numpy()
+    assert _scan_blocks(grid.shape) > 1024
+    rng = np.random.RandomState(288)
+    deform = (0.3 * rng.randn(*grid.shape, 3)).astype(np.float32) if with_deform else None
+    v, f, rec = _bit_exact(grid, 0.0, deform, True)
+    assert len(f) > 100000
+    w = rng.randn(*v.shape).astype(np.float32)
+    dg, dd = _grads(grid, deform, 0.0, True, w)
+    ref_g, ref_d = R.backward(rec, w, with_deform)
+    err = np.abs(dg - ref_g).max() / np.abs(ref_g).max()
+    print(f"DiffMC backward 288^3 dgrid: err {err:.3e} of max, bound 1e-6")
+    assert err <= 1e-6
+    if with_deform:
+        err = np.abs(dd - ref_d).max() / np.abs(ref_d).max()
+        print(f"DiffMC backward 288^3 ddeform: err {err:.3e} of max, bound 1e-6")
+        assert err <= 1e-6
+    dg2, dd2 = _grads(grid, deform, 0.0, True, w)
+    assert np.array_equal(dg, dg2) and (dd is None or np.array_equal(dd, dd2))
