@@ -96,6 +96,14 @@ SYMBOLS = {
     "dgm_mc_count": (_i, [_i, _i, _i, _vp, _f, _vp, _vp, _vp]),
     "dgm_mc_emit": (_i, [_i, _i, _i, _vp, _vp, _f, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "dgm_mc_backward": (_i, [_i, _i, _i, _vp, _vp, _f, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "dgm_tri_raster_scratch_bytes": (_c.c_size_t, [_i, _i, _i]),
+    "dgm_tri_rasterize_forward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_tri_rasterize_backward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_tri_interpolate_forward": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_tri_interpolate_backward": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_tri_aa_scratch_bytes": (_c.c_size_t, [_i]),
+    "dgm_tri_antialias_forward": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_tri_antialias_backward": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dgm_mlp_set_gemm": (_i, [_i]),
     "dgm_timenet_forward": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "dgm_timenet_backward": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

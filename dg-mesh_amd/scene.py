@@ -439,7 +439,7 @@ def ssim(img1, img2, window_size=11, size_average=True):
 class TorchCamera:
     """GPU-resident view of synthetic.Camera with the attribute names of R/scene/cameras.py:18-71."""
 
-    def __init__(self, cam, device, original_image=None):
+    def __init__(self, cam, device, original_image=None, gt_alpha_mask=None):
         self.FoVx, self.FoVy = cam.FoVx, cam.FoVy
         self.image_width, self.image_height = cam.image_width, cam.image_height
         self.world_view_transform = torch.tensor(cam.world_view_transform, device=device)
@@ -447,3 +447,5 @@ class TorchCamera:
         self.camera_center = torch.tensor(cam.camera_center, device=device)
         self.fid = torch.tensor([cam.fid], dtype=torch.float32, device=device)
         self.original_image = None if original_image is None else torch.as_tensor(original_image, device=device).clamp(0.0, 1.0)
+        # (H, W, 1) as the reference Camera's gt_alpha_mask; the target of MeshPhase(mesh_losses="render")'s mask loss
+        self.gt_alpha_mask = None if gt_alpha_mask is None else torch.as_tensor(gt_alpha_mask, dtype=torch.float32, device=device)

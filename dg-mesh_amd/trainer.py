@@ -17,8 +17,14 @@ third-party packages outside the reference (parity unpinne
     at isovalue 0 and mapped to world space like R/utils/renderer.py:171-174; deform_back + appearance run on its vertices and the
     Laplacian regulariser on its faces (R/train.py:278-285), so those terms reach the density threshold, the normals and the
     positions through DiffMC and DPSR.
-nvdiffrast is not rebuilt in either: L1 losses against fixed targets stand in for the mask / mesh-image losses, and their numbers
-mean nothing.
+The mask / mesh-image losses come from one of two modes (`mesh_losses`):
+  * "stand_in" (default): L1 losses against fixed targets stand in for them (nvdiffrast is not rebuilt in this mode), and their
+    numbers mean nothing;
+  * "render" (mesh_source="diffmc" only): the DiffMC mesh is rendered from the frame's camera with the appearance colours by this
+    project's rasterizer (mesh_raster.py, csrc/mesh_raster.hip: rasterize -> interpolate -> antialias) and the reference's terms
+    are computed (R/train.py:264-275): mask_loss = L1(mask, gt_alpha_mask) * 100 * mask_loss_weight, mesh_img_loss =
+    ((1 - lambda) L1 + lambda (1 - SSIM))(mesh image, original_image) * mesh_img_loss_weight; the cameras must carry a
+    gt_alpha_mask (H, W, 1).
 Host synchronisations of the reference's loop that do not change results are dropped
 (torch.cuda.empty_cache() every iteration, R/train.py:130; get_psnr's .item(), :315).
 
@@ -126,10 +132,14 @@ class MeshPhase:
 
     def __init__(self, deform_normal, deform_back_normal, appearance, dpsr=None, n_verts=20000, density_thres=None,
                  center=None, scale=None, seed=0, device="cuda", stand_in_weight=1e-6, mesh_source="probes",
-                 laplacian_loss_weight=1.0):
+                 laplacian_loss_weight=1.0, mesh_losses="stand_in"):
         if mesh_source not in ("probes", "diffmc"):
             raise ValueError(f"MeshPhase: mesh_source must be 'probes' or 'diffmc', got {mesh_source!r}")
-        self.stand_in_weight = stand_in_weight
+        if mesh_losses not in ("stand_in", "render"):
+            raise ValueError(f"MeshPhase: mesh_losses must be 'stand_in' or 'render', got {mesh_losses!r}")
+        if mesh_losses == "render" and mesh_source != "diffmc":
+            raise ValueError("MeshPhase: mesh_losses='render' renders the DiffMC mesh: it needs mesh_source='diffmc'")
+        self.stand_in_weight, self.mesh_losses = stand_in_weight, mesh_losses
         self.mesh_source, self.laplacian_loss_weight = mesh_source, laplacian_loss_weight
         from .marching_cubes import DiffMC
         self.diffmc = DiffMC(dtype=torch.float32)  # (stateless; also used by extract_mesh)
@@ -465,10 +475,14 @@ class Trainer:
 
     def diffmc_terms(self, cam, iteration, losses, psr):
         """mesh_source="diffmc": the mesh of phi (R/utils/renderer.py:171-181), the vertex colours and the Laplacian regulariser
-        (R/train.py:278-285, with its (1 - iteration / iterations) decay); the mask / mesh-image stand-ins are fixed functions of
-        the vertex positions (V changes every step)."""
+        (R/train.py:278-285, with its (1 - iteration / iterations) decay).  mesh_losses="stand_in": the mask / mesh-image stand-ins
+        are fixed functions of the vertex positions (V changes every step); "render": the mesh rendered from `cam` against its
+        gt_alpha_mask and original_image (R/train.py:264-275)."""
         from .dpsr import laplace_regularizer_const
         opt, ms = self.opt, self.mesh
+        if ms.mesh_losses == "render" and getattr(cam, "gt_alpha_mask", None) is None:
+            raise RuntimeError("MeshPhase(mesh_losses='render') needs a mask on every camera: build them with "
+                               "TorchCamera(..., gt_alpha_mask=<(H, W, 1) tensor>)")
         verts, faces = ms.surface(self.g, psr)
         ms.last_mesh = (verts.detach(), faces)
         V = verts.shape[0]
@@ -477,11 +491,18 @@ class Trainer:
         t_v = cam.fid.reshape(1, 1).expand(V, -1)
         back_v = self.deform_back.step(verts.detach(), t_v)[0]                            # R/utils/renderer.py:179-181
         vtx_color = ms.appearance.step(verts + back_v, t_v)
-        u = (verts - self.g.gaussian_center) / self.g.gaussian_scale                      # [-1, 1]
-        radius = u.norm(dim=1)
-        losses["mask_loss"] = S.l1_loss(radius, torch.full_like(radius, 0.5)) * 100 * opt.mask_loss_weight * ms.stand_in_weight
-        color_target = 0.5 + 0.5 * torch.sin(3.0 * u.detach())
-        losses["mesh_img_loss"] = S.l1_loss(vtx_color, color_target) * opt.mesh_img_loss_weight * (1e3 * ms.stand_in_weight)
+        if ms.mesh_losses == "render":                                                    # R/utils/renderer.py:209-230
+            from .loss import image_loss
+            from .mesh_raster import render_mask_and_mesh
+            mask, mesh_image = render_mask_and_mesh(None, verts, faces, vtx_color, cam, whitebackground=self.white_background)
+            losses["mask_loss"] = S.l1_loss(mask, cam.gt_alpha_mask) * 100 * opt.mask_loss_weight
+            losses["mesh_img_loss"] = image_loss(mesh_image, cam.original_image, opt.lambda_dssim) * opt.mesh_img_loss_weight
+        else:
+            u = (verts - self.g.gaussian_center) / self.g.gaussian_scale                  # [-1, 1]
+            radius = u.norm(dim=1)
+            losses["mask_loss"] = S.l1_loss(radius, torch.full_like(radius, 0.5)) * 100 * opt.mask_loss_weight * ms.stand_in_weight
+            color_target = 0.5 + 0.5 * torch.sin(3.0 * u.detach())
+            losses["mesh_img_loss"] = S.l1_loss(vtx_color, color_target) * opt.mesh_img_loss_weight * (1e3 * ms.stand_in_weight)
         t_iter = iteration / opt.iterations
         losses["laplacian_loss"] = laplace_regularizer_const(verts, faces) * (1000 * ms.laplacian_loss_weight) * (1 - t_iter)
 

@@ -54,7 +54,8 @@ extern "C" {
  *   5: dgm_rasterize_forward_capacity added (a forward that never waits for the device); dgm_se3_* added (6-DoF heads);
  *      dgm_mlp_set_gemm knows modes 4 and 5.
  *      Every entry point of 4 is unchanged.
- *      Later additions that leave every existing entry point and layout unchanged keep the number: dgm_mc_* (marching cubes). */
+ *      Later additions that leave every existing entry point and layout unchanged keep the number: dgm_mc_* (marching cubes),
+ *      dgm_tri_* (mesh rasterizer). */
 #define DGM_ABI_VERSION 5
 
 /* Allocator callback: must return a device pointer to at least `bytes` bytes (128-byte aligned),
@@ -440,6 +441,38 @@ int dgm_mc_emit(int X, int Y, int Z, const float* grid, const float* deform, flo
                 float* verts, int* faces, void* stream);
 int dgm_mc_backward(int X, int Y, int Z, const float* grid, const float* deform, float iso, int normalize, const char* scratch, int V,
                     const float* dverts, float* dgrid, float* ddeform, void* stream);
+
+/* ---- mesh rasterizer (csrc/mesh_raster.hip) ---------------------------------------------------------------------------------
+ * Replaces nvdiffrast's rasterize / interpolate / antialias (dgmesh/utils/renderer.py:33-121), batch size 1.  pos (V, 4) fp32
+ * clip-space positions, tri (F, 3) int32, F < 2^24, 0 < H, W <= 16384.  Screen s = ((x/w + 1) W/2, (y/w + 1) H/2); pixel (px, py)
+ * is centred at (px + .5, py + .5), row 0 at NDC y = -1.  A face with a vertex at w <= 0 (or an index outside [0, V), or zero
+ * screen area) is dropped.  A centre is covered when the three oriented edge functions, each evaluated with its endpoints in
+ * ascending vertex-id order, are >= 0.  Depth z/w, linear in screen space; the smaller wins, ties to the lower face id.
+ *   dgm_tri_raster_scratch_bytes: device scratch of one rasterize forward (0 for invalid sizes).
+ *   dgm_tri_rasterize_forward : rast (H, W, 4) = (u, v, z/w, id + 1), zeros on background; (u, v) perspective-correct
+ *                               barycentrics of vertices 0 and 1.  Bit-reproducible.
+ *   dgm_tri_rasterize_backward: dpos (V, 4) (overwritten) = the gradient of sum(drast[..., 0:2] * rast[..., 0:2]) w.r.t. x, y, w;
+ *                               the z column is zero.
+ *   dgm_tri_interpolate_*     : out (H, W, C) = u a0 + v a1 + (1 - u - v) a2 (zeros on background); backward writes dattr (V, C)
+ *                               and drast (H, W, 4) (channels 2, 3 zero), both overwritten.
+ *   dgm_tri_aa_scratch_bytes: device scratch of one antialias forward (the edge topology); its backward reads it again.
+ *   dgm_tri_antialias_forward : out (H, W, C) = color + the analytic blend across silhouette edges (csrc/mesh_raster.hip).
+ *                               Bit-reproducible.
+ *   dgm_tri_antialias_backward: dcolor (H, W, C) (a gather, bit-reproducible) and dpos (V, 4) (overwritten).
+ * dpos and dattr are summed with fp32 atomics: they agree to rounding, not bit for bit, run to run. */
+size_t dgm_tri_raster_scratch_bytes(int F, int H, int W);
+int dgm_tri_rasterize_forward(int V, int F, int H, int W, const float* pos, const int* tri, char* scratch, float* rast, void* stream);
+int dgm_tri_rasterize_backward(int V, int F, int H, int W, const float* pos, const int* tri, const float* rast, const float* drast,
+                               float* dpos, void* stream);
+int dgm_tri_interpolate_forward(int V, int F, int H, int W, int C, const float* attr, const float* rast, const int* tri, float* out,
+                                void* stream);
+int dgm_tri_interpolate_backward(int V, int F, int H, int W, int C, const float* attr, const float* rast, const int* tri,
+                                 const float* dout, float* dattr, float* drast, void* stream);
+size_t dgm_tri_aa_scratch_bytes(int F);
+int dgm_tri_antialias_forward(int V, int F, int H, int W, int C, const float* color, const float* rast, const float* pos, const int* tri,
+                              char* scratch, float* out, void* stream);
+int dgm_tri_antialias_backward(int V, int F, int H, int W, int C, const float* color, const float* rast, const float* pos, const int* tri,
+                               const char* scratch, const float* dout, float* dcolor, float* dpos, void* stream);
 
 #ifdef __cplusplus
 }
