@@ -104,6 +104,11 @@ SYMBOLS = {
     "dgm_tri_aa_scratch_bytes": (_c.c_size_t, [_i]),
     "dgm_tri_antialias_forward": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dgm_tri_antialias_backward": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_anchor_face_geometry": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_anchor_nn_scratch_bytes": (_c.c_size_t, [_i, _i]),
+    "dgm_anchor_nn": (_i, [_i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
+    "dgm_anchor_classify_scratch_bytes": (_c.c_size_t, [_i, _i]),
+    "dgm_anchor_classify": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dgm_mlp_set_gemm": (_i, [_i]),
     "dgm_timenet_forward": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "dgm_timenet_backward": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

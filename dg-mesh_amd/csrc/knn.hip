@@ -231,6 +231,29 @@ knn_search_kernel(int P, int nboxes, const float4* __restrict__ sorted, const fl
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
+size_t radix_sort_hist_words(int n) { return (size_t)256 * ((n + RS_TILE - 1) / RS_TILE); }
+
+// Stable LSD sort of n (key, value) pairs on the low 8 * passes key bits; A and B buffers alternate, the result lies in the
+// returned value buffer (its keys in the matching key buffer).  hist / scanned: radix_sort_hist_words(n) u32 each.
+const unsigned* radix_sort_pairs(hipStream_t st, int n, int passes, unsigned* keysA, unsigned* valsA, unsigned* keysB,
+                                 unsigned* valsB, unsigned* hist, unsigned* scanned) {
+    const int nblk = (n + RS_TILE - 1) / RS_TILE;
+    unsigned *kin = keysA, *kout = keysB, *vin = valsA, *vout = valsB;
+    for (int pass = 0; pass < passes; pass++) {
+        hipLaunchKernelGGL(rs_hist_kernel, dim3(nblk), dim3(256), 0, st, n, pass * 8, nblk, kin, hist);
+        launch_scan_blocks(st, 256 * nblk, hist, scanned, nullptr);
+        hipLaunchKernelGGL(rs_scatter_kernel, dim3(nblk), dim3(256), 0, st, n, pass * 8, nblk, kin, vin, scanned, kout,
+                           vout);
+        unsigned* t = kin;
+        kin = kout;
+        kout = t;
+        t = vin;
+        vin = vout;
+        vout = t;
+    }
+    return vin;
+}
+
 size_t knn_scratch_bytes(int P) {
     const size_t n = (size_t)P;
     const size_t nblk = (n + RS_TILE - 1) / RS_TILE;
@@ -275,19 +298,7 @@ void launch_knn(hipStream_t st, int P, const float* pts, float* dists, char* scr
     hipLaunchKernelGGL(knn_bbox_partial_kernel, dim3(nparts), dim3(256), 0, st, P, pts, partial);
     hipLaunchKernelGGL(knn_bbox_final_kernel, dim3(1), dim3(64), 0, st, nparts, partial, bbox);
     hipLaunchKernelGGL(knn_morton_kernel, dim3((P + 255) / 256), dim3(256), 0, st, P, pts, bbox, codesA, idxA);
-    unsigned *kin = codesA, *kout = codesB, *vin = idxA, *vout = idxB;
-    for (int pass = 0; pass < 4; pass++) {
-        hipLaunchKernelGGL(rs_hist_kernel, dim3(nblk), dim3(256), 0, st, P, pass * 8, nblk, kin, hist);
-        launch_scan_blocks(st, 256 * nblk, hist, scanned, nullptr);
-        hipLaunchKernelGGL(rs_scatter_kernel, dim3(nblk), dim3(256), 0, st, P, pass * 8, nblk, kin, vin, scanned, kout,
-                           vout);
-        unsigned* t = kin;
-        kin = kout;
-        kout = t;
-        t = vin;
-        vin = vout;
-        vout = t;
-    }
+    const unsigned* vin = radix_sort_pairs(st, P, 4, codesA, idxA, codesB, idxB, hist, scanned);
     hipLaunchKernelGGL(knn_box_kernel, dim3(nboxes), dim3(KNN_BOX), 0, st, P, pts, vin, sorted, boxes);
     hipLaunchKernelGGL(knn_search_kernel, dim3((P + 255) / 256), dim3(256), 0, st, P, nboxes, sorted, boxes, dists);
 }

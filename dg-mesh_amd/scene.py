@@ -210,6 +210,13 @@ class GaussianModel:
         from . import densify
         densify.reset_opacity(self)
 
+    def anchor_mesh(self, verts, faces, deform, deform_back, t, search_radius=0.0005, topn=2, bs=256, increase_bs=1024,
+                    generator=None):
+        """Gaussian-mesh anchoring (gaussian_model_dpsr_dynamic_anchor.py:745-829) on the device: plans and applies at once and
+        returns the anchor loss (anchor.py; the trainer plans before backward and applies after it)."""
+        from . import anchor
+        return anchor.anchor_mesh(self, verts, faces, deform, deform_back, t, search_radius, topn, bs, increase_bs, generator)
+
     def add_densification_stats(self, viewspace_point_tensor, update_filter):
         self.xyz_gradient_accum[update_filter] += torch.norm(viewspace_point_tensor.grad[update_filter, :2], dim=-1,
                                                               keepdim=True)
@@ -277,6 +284,14 @@ class OptimizationParams:
     normal_deform_delay = 2000   # NORMAL_WARMUP_ITER of R/train.py:127: deform_normal / deform_back_normal start this long after dpsr_iter
     mask_loss_weight = 10.0
     mesh_img_loss_weight = 1.0
+    # Gaussian-mesh anchoring (R/arguments/__init__.py, R/train.py:286-304); runs only with MeshPhase(anchor=True)
+    use_anchor = 1.0
+    anchor_iter = 8000
+    anchor_interval = 100
+    anchor_search_radius = 0.0005
+    anchor_topn = 2
+    anchor_n_1_bs = 512
+    anchor_0_1_bs = 1024
 
 
 def covariance_from_scaling_rotation(scaling, scaling_modifier, rotation):

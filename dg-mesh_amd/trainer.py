@@ -25,6 +25,14 @@ The mask / mesh-image losses come from one of two modes (`mesh_losses`):
     are computed (R/train.py:264-275): mask_loss = L1(mask, gt_alpha_mask) * 100 * mask_loss_weight, mesh_img_loss =
     ((1 - lambda) L1 + lambda (1 - SSIM))(mesh image, original_image) * mesh_img_loss_weight; the cameras must carry a
     gt_alpha_mask (H, W, 1).
+Gaussian-mesh anchoring (`MeshPhase(anchor=True)`, mesh_source="diffmc" only, off by default; R/train.py:286-304): on iterations
+> anchor_iter that are multiples of anchor_interval (use_anchor > 0) the Gaussians are matched to the faces of this step's DiffMC
+mesh at the frame's fid (anchor.py).  The plan is built in the loss computation and adds losses["anchor_loss"] = 0.1 * anchor_loss;
+its surgery runs after backward and before the Adam step, through the same re-binding as densification, so the Gaussians get no
+update on that iteration (their Parameters are replaced) while the networks and the density threshold step.  The densification
+statistics and decision of an anchoring iteration are skipped (the reference would index the new set with the old visibility mask).
+With several ranks, rank 0's (verts, faces, fid) are broadcast, every rank plans from them with an anchoring generator seeded alike,
+and only rank 0 adds the anchor loss, so the summed gradient carries one anchor term and the replicas stay identical.
 Host synchronisations of the reference's loop that do not change results are dropped
 (torch.cuda.empty_cache() every iteration, R/train.py:130; get_psnr's .item(), :315).
 
@@ -132,13 +140,17 @@ class MeshPhase:
 
     def __init__(self, deform_normal, deform_back_normal, appearance, dpsr=None, n_verts=20000, density_thres=None,
                  center=None, scale=None, seed=0, device="cuda", stand_in_weight=1e-6, mesh_source="probes",
-                 laplacian_loss_weight=1.0, mesh_losses="stand_in"):
+                 laplacian_loss_weight=1.0, mesh_losses="stand_in", *, anchor=False):
         if mesh_source not in ("probes", "diffmc"):
             raise ValueError(f"MeshPhase: mesh_source must be 'probes' or 'diffmc', got {mesh_source!r}")
         if mesh_losses not in ("stand_in", "render"):
             raise ValueError(f"MeshPhase: mesh_losses must be 'stand_in' or 'render', got {mesh_losses!r}")
         if mesh_losses == "render" and mesh_source != "diffmc":
             raise ValueError("MeshPhase: mesh_losses='render' renders the DiffMC mesh: it needs mesh_source='diffmc'")
+        if anchor and mesh_source != "diffmc":
+            raise ValueError("MeshPhase: anchor=True anchors the Gaussians to the DiffMC mesh: it needs mesh_source='diffmc'")
+        self.anchor = bool(anchor)
+        self.last_anchor = None  # (verts, faces, fid) of the latest anchoring event
         self.stand_in_weight, self.mesh_losses = stand_in_weight, mesh_losses
         self.mesh_source, self.laplacian_loss_weight = mesh_source, laplacian_loss_weight
         from .marching_cubes import DiffMC
@@ -254,6 +266,13 @@ class Trainer:
         if dev.type == "cuda":
             self.densify_generator = torch.Generator(device=dev)
             self.densify_generator.manual_seed(1234567 + seed)
+        # permutations and angles of Gaussian-mesh anchoring: seeded alike on every rank, like densify_generator
+        self.anchor_generator = None
+        self._anchor_plan = None
+        self.last_anchor_info = None
+        if dev.type == "cuda":
+            self.anchor_generator = torch.Generator(device=dev)
+            self.anchor_generator.manual_seed(7654321 + seed)
         self.time_interval = 1.0 / max(len(cameras), 1)
         from .deform import get_linear_noise_func
         self.smooth_term = get_linear_noise_func(lr_init=0.1, lr_final=1e-15, lr_delay_mult=0.01, max_steps=20000)
@@ -309,6 +328,42 @@ class Trainer:
         if e["left"] == 0:
             e["views"] = e["g"].pack()
             e["work"] = dist.all_reduce(e["g"].flat, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
+
+    def anchor_due(self, iteration):
+        """R/train.py:286-291: anchoring runs on this iteration (MeshPhase(anchor=True), inside the mesh phase)."""
+        opt, ms = self.opt, self.mesh
+        return (ms is not None and ms.anchor and ms.dpsr is not None and iteration >= opt.dpsr_iter and iteration > opt.anchor_iter
+                and iteration % opt.anchor_interval == 0 and opt.use_anchor > 0)
+
+    def _shared_mesh(self, verts, faces, fid):
+        """Rank 0's (verts, faces, fid), sizes first, on every rank."""
+        if self.world == 1:
+            return verts, faces, fid
+        dev = verts.device
+        sizes = torch.tensor([verts.shape[0], faces.shape[0]], dtype=torch.int64, device=dev)
+        dist.broadcast(sizes, 0, group=self.group)
+        V, F = (int(v) for v in sizes.tolist())
+        if self.rank != 0:
+            verts = torch.empty((V, 3), dtype=torch.float32, device=dev)
+            faces = torch.empty((F, 3), dtype=torch.int32, device=dev)
+        verts, faces = verts.contiguous(), faces.to(torch.int32).contiguous()
+        fid = fid.detach().reshape(1).to(torch.float32).clone()
+        for t in (verts, faces, fid):
+            if t.numel():
+                dist.broadcast(t, 0, group=self.group)
+        return verts, faces, fid.reshape(())
+
+    def anchor_terms(self, cam, iteration, losses, verts, faces):
+        """Plan this iteration's anchoring from the step's DiffMC mesh at the frame's fid (R/train.py:292-304); step() applies it."""
+        from .anchor import plan_anchor
+        opt = self.opt
+        verts, faces, fid = self._shared_mesh(verts.detach(), faces, cam.fid)
+        self.mesh.last_anchor = (verts, faces, fid)
+        self._anchor_plan = plan_anchor(self.g, verts, faces, self.deform, self.deform_back, fid,
+                                        search_radius=opt.anchor_search_radius, topn=opt.anchor_topn, bs=opt.anchor_n_1_bs,
+                                        increase_bs=opt.anchor_0_1_bs, generator=self.anchor_generator)
+        if self.rank == 0:
+            losses["anchor_loss"] = self._anchor_plan["loss"] * 0.1
 
     def maybe_densify(self, iteration):
         """R/train.py:499-515: every densification_interval iterations after densify_from_iter clone / split / prune
@@ -485,6 +540,8 @@ class Trainer:
                                "TorchCamera(..., gt_alpha_mask=<(H, W, 1) tensor>)")
         verts, faces = ms.surface(self.g, psr)
         ms.last_mesh = (verts.detach(), faces)
+        if self.anchor_due(iteration):
+            self.anchor_terms(cam, iteration, losses, verts, faces)
         V = verts.shape[0]
         if V == 0:  # (an empty surface: nothing for the vertex networks or the regulariser to see)
             return
@@ -524,7 +581,9 @@ class Trainer:
         # on the device, so its gradients are discarded and the frame is rendered again with the raised capacity.  (With the
         # Gaussian bucket's early all-reduce armed the check stays inside the forward call: a discarded backward must not have
         # started a collective the other ranks do not repeat.)
-        defer = _RZ.SYNC_FREE and not (self.world > 1 and self._early is not None)
+        # (an anchoring iteration is never redone: its plan draws random numbers and, with several ranks, broadcasts)
+        anchoring = self.anchor_due(iteration)
+        defer = _RZ.SYNC_FREE and not (self.world > 1 and self._early is not None) and not anchoring
         for _attempt in range(4):
             if self.pack:
                 for p in self.params:
@@ -554,7 +613,12 @@ class Trainer:
         else:
             raise RuntimeError("rasterizer capacity: a frame overflowed four times in a row")
         rebound = False
-        if self.track_stats and iteration < self.opt.densify_until_iter:  # R/train.py:488-496
+        plan, self._anchor_plan = self._anchor_plan, None
+        if plan is not None:  # Gaussian-mesh anchoring: the surgery, after backward, before the Adam step; no densify this iteration
+            from .anchor import apply_anchor
+            self.last_anchor_info = apply_anchor(g, plan)
+            rebound = True
+        elif self.track_stats and iteration < self.opt.densify_until_iter:  # R/train.py:488-496
             g.track_densification_stats(pkg.get("viewspace_points"), pkg.get("visibility_filter"), pkg["radii"])
             if self.densify:
                 rebound = self.maybe_densify(iteration)

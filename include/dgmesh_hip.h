@@ -55,7 +55,7 @@ extern "C" {
  *      dgm_mlp_set_gemm knows modes 4 and 5.
  *      Every entry point of 4 is unchanged.
  *      Later additions that leave every existing entry point and layout unchanged keep the number: dgm_mc_* (marching cubes),
- *      dgm_tri_* (mesh rasterizer). */
+ *      dgm_tri_* (mesh rasterizer), dgm_anchor_* (Gaussian-mesh anchoring). */
 #define DGM_ABI_VERSION 5
 
 /* Allocator callback: must return a device pointer to at least `bytes` bytes (128-byte aligned),
@@ -473,6 +473,31 @@ int dgm_tri_antialias_forward(int V, int F, int H, int W, int C, const float* co
                               char* scratch, float* out, void* stream);
 int dgm_tri_antialias_backward(int V, int F, int H, int W, int C, const float* color, const float* rast, const float* pos, const int* tri,
                                const char* scratch, const float* dout, float* dcolor, float* dpos, void* stream);
+
+/* ---- Gaussian-mesh anchoring (csrc/anchor.hip) --------------------------------------------------------------------------------
+ * Replace the trimesh / pytorch3d.knn_points / torch.unique work of GaussianModelDPSRDynamicAnchor.anchor_mesh
+ * (dgmesh/scene/gaussian_model_dpsr_dynamic_anchor.py:745-829).  Every buffer is device memory; nothing is read back.
+ *   dgm_anchor_face_geometry: centroids (F, 3) = ((v0 + v1) + v2) / 3 and unit normals (F, 3) of cross(v1 - v0, v2 - v0), zero where
+ *       the cross product has zero length (trimesh's face_normals).  A face with an index outside [0, V) gets a NaN centroid (no
+ *       query can choose it) and a zero normal.  fp32, no FMA.
+ *   dgm_anchor_nn: for each of Nq query points (Nq, 3), idx[q] = the target (Nt, 3) with the least d2 = (dx*dx + dy*dy) + dz*dz (fp32,
+ *       no FMA), ties to the smallest target index, reported only if d2 < max_d2 (strict); otherwise idx = -1, d2 = +inf.  max_d2 may
+ *       be +inf (the unbounded search).  Bit-reproducible; independent of the targets' order up to the index mapping.
+ *       scratch: dgm_anchor_nn_scratch_bytes(Nq, Nt) bytes (unused for max_d2 = +inf, may then be NULL).
+ *   dgm_anchor_classify: face_of (P) int32 (the Gaussian's face, -1 or out of [0, F): invalid) ->
+ *       counts (F) = valid Gaussians per face; offsets (F) = exclusive prefix sum of counts;
+ *       lists (F) = [faces with count 1 | count > 1 | count 0], each part ascending;
+ *       members (P) = the valid Gaussians grouped by face, ascending face, ascending index within a face (members[offsets[f] + r]
+ *       is the r-th Gaussian of face f), then -1;  rank (P) = r for a valid Gaussian, -1 otherwise;
+ *       totals (4) = (n_1_1, n_n_1, n_0_1, valid Gaussians) -- the caller's one read-back.
+ *       scratch: dgm_anchor_classify_scratch_bytes(P, F) bytes. */
+int dgm_anchor_face_geometry(int V, int F, const float* verts, const int* faces, float* centroids, float* normals, void* stream);
+size_t dgm_anchor_nn_scratch_bytes(int Nq, int Nt);
+int dgm_anchor_nn(int Nq, int Nt, const float* queries, const float* targets, float max_d2, char* scratch, int* idx, float* d2,
+                  void* stream);
+size_t dgm_anchor_classify_scratch_bytes(int P, int F);
+int dgm_anchor_classify(int P, int F, const int* face_of, char* scratch, int* counts, int* offsets, int* lists, int* members, int* rank,
+                        int* totals, void* stream);
 
 #ifdef __cplusplus
 }
