@@ -109,6 +109,12 @@ SYMBOLS = {
     "dgm_anchor_nn": (_i, [_i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
     "dgm_anchor_classify_scratch_bytes": (_c.c_size_t, [_i, _i]),
     "dgm_anchor_classify": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_ninit_bbox_scratch_bytes": (_c.c_size_t, []),
+    "dgm_ninit_bbox": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_ninit_face_areas": (_i, [_i, _i, _vp, _vp, _vp, _vp]),
+    "dgm_ninit_scan_scratch_bytes": (_c.c_size_t, [_i]),
+    "dgm_ninit_area_scan": (_i, [_i, _vp, _vp, _vp, _vp]),
+    "dgm_ninit_sample": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dgm_mlp_set_gemm": (_i, [_i]),
     "dgm_timenet_forward": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "dgm_timenet_backward": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -10,6 +10,19 @@ import torch
 from . import _lib
 
 
+_COORDS = {}
+
+
+def _coords(bbox_scale, resolution, dev):
+    """The grid coordinates, computed like the reference, on the host.  Uploaded once per (box, resolution, device), from pinned
+    memory without blocking, so that no call waits for the device."""
+    key = (bbox_scale, resolution, dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+    c = _COORDS.get(key)
+    if c is None:
+        c = _COORDS[key] = torch.linspace(-bbox_scale, bbox_scale, resolution).pin_memory().to(dev, non_blocking=True)
+    return c
+
+
 def get_opacity_field_from_gaussians(xyzs, rotations, scalings, opacities, resolution=256, num_blocks=16, relax_ratio=0.5,
                                      opacity_threshold=0.005, bbox_scale=1.25):
     if not xyzs.is_cuda:
@@ -21,7 +34,7 @@ def get_opacity_field_from_gaussians(xyzs, rotations, scalings, opacities, resol
     f = lambda t: t.detach().to(torch.float32).contiguous()
     xyzs, rotations, scalings, opacities = f(xyzs), f(rotations), f(scalings), f(opacities)
     P = xyzs.shape[0]
-    coords = torch.linspace(-bbox_scale, bbox_scale, resolution).to(dev)   # computed like the reference, on the host
+    coords = _coords(float(bbox_scale), int(resolution), dev)
     occ = torch.empty([resolution] * 3, dtype=torch.float32, device=dev)
     scratch = torch.empty(L.dgm_opacity_field_scratch_bytes(P), dtype=torch.uint8, device=dev)
     vp = lambda t: ctypes.c_void_p(t.data_ptr())

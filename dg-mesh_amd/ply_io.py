@@ -183,3 +183,25 @@ def read_mesh_ply(path):
     if nf and (f["n"] != 3).any():
         raise ValueError(f"{path}: only triangles are supported")
     return verts, f["idx"].astype(np.int32).reshape(-1, 3)
+
+
+# ---- point clouds with normals (pointcloud_init.ply of normal_initialization, R/scene/gaussian_model_dpsr_dynamic_anchor.py:722-729) --
+def write_pointcloud_ply(path, points, normals):
+    """points (N, 3), normals (N, 3) (numpy arrays or tensors on any device) as `element vertex N` with float x y z nx ny nz,
+    binary_little_endian -- the layout Open3D's write_point_cloud produces for a cloud with normals, up to its double precision."""
+    as_np = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+    p = np.asarray(as_np(points), np.float32).reshape(-1, 3)
+    n = np.asarray(as_np(normals), np.float32).reshape(-1, 3)
+    if len(p) != len(n):
+        raise ValueError(f"write_pointcloud_ply: {len(p)} points but {len(n)} normals")
+    vertex = np.empty(len(p), dtype=[(k, "<f4") for k in ("x", "y", "z", "nx", "ny", "nz")])
+    for i, k in enumerate(("x", "y", "z")):
+        vertex[k], vertex["n" + k] = p[:, i], n[:, i]
+    write_ply(path, [("vertex", vertex)])
+
+
+def read_pointcloud_ply(path):
+    """-> points (N, 3) float32, normals (N, 3) float32 of a PLY as write_pointcloud_ply writes it."""
+    v = read_ply(path)["vertex"]
+    col = lambda k: np.asarray(v[k], np.float32)
+    return np.stack([col("x"), col("y"), col("z")], 1), np.stack([col("nx"), col("ny"), col("nz")], 1)

@@ -284,6 +284,7 @@ class OptimizationParams:
     normal_deform_delay = 2000   # NORMAL_WARMUP_ITER of R/train.py:127: deform_normal / deform_back_normal start this long after dpsr_iter
     mask_loss_weight = 10.0
     mesh_img_loss_weight = 1.0
+    init_density_threshold = 0.05   # R/arguments/__init__.py:144: set by normal_initialization at dpsr_iter (normal_init.py)
     # Gaussian-mesh anchoring (R/arguments/__init__.py, R/train.py:286-304); runs only with MeshPhase(anchor=True)
     use_anchor = 1.0
     anchor_iter = 8000

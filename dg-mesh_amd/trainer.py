@@ -33,6 +33,13 @@ update on that iteration (their Parameters are replaced) while the networks and 
 statistics and decision of an anchoring iteration are skipped (the reference would index the new set with the old visibility mask).
 With several ranks, rank 0's (verts, faces, fid) are broadcast, every rank plans from them with an anchoring generator seeded alike,
 and only rank 0 adds the anchor loss, so the summed gradient carries one anchor term and the replicas stay identical.
+Entering the phase (`MeshPhase(normal_init=True)`, mesh_source="diffmc" with a DPSR module, off by default; R/train.py:242-246): at
+iteration == dpsr_iter, after the render / cycle terms and before the first mesh terms, normal_init.normal_initialization measures
+gaussian_center / gaussian_scale, gives every Gaussian the normal of the nearest sample of the opacity field's surface and sets the
+density threshold to opt.init_density_threshold, with this iteration's deformation -- so a Trainer started in the Gaussian-only phase
+crosses dpsr_iter without being handed center / scale / density_thres.  The step draws random numbers (its own generator, seeded
+alike on every rank), so that iteration is never redone by the sync-free forward; with several ranks every rank runs the chain (its
+frame, hence its d_xyz, differs) and rank 0's normals, centre, scale and threshold are broadcast.
 Host synchronisations of the reference's loop that do not change results are dropped
 (torch.cuda.empty_cache() every iteration, R/train.py:130; get_psnr's .item(), :315).
 
@@ -140,7 +147,7 @@ class MeshPhase:
 
     def __init__(self, deform_normal, deform_back_normal, appearance, dpsr=None, n_verts=20000, density_thres=None,
                  center=None, scale=None, seed=0, device="cuda", stand_in_weight=1e-6, mesh_source="probes",
-                 laplacian_loss_weight=1.0, mesh_losses="stand_in", *, anchor=False):
+                 laplacian_loss_weight=1.0, mesh_losses="stand_in", *, anchor=False, normal_init=False, gaussian_ratio=1.1, real=False):
         if mesh_source not in ("probes", "diffmc"):
             raise ValueError(f"MeshPhase: mesh_source must be 'probes' or 'diffmc', got {mesh_source!r}")
         if mesh_losses not in ("stand_in", "render"):
@@ -149,7 +156,15 @@ class MeshPhase:
             raise ValueError("MeshPhase: mesh_losses='render' renders the DiffMC mesh: it needs mesh_source='diffmc'")
         if anchor and mesh_source != "diffmc":
             raise ValueError("MeshPhase: anchor=True anchors the Gaussians to the DiffMC mesh: it needs mesh_source='diffmc'")
+        if normal_init and (mesh_source != "diffmc" or dpsr is None):
+            raise ValueError("MeshPhase: normal_init=True starts the DPSR -> DiffMC chain at dpsr_iter: it needs a DPSR module and "
+                             "mesh_source='diffmc'")
         self.anchor = bool(anchor)
+        # normal_initialization at iteration == dpsr_iter (normal_init.py); gaussian_ratio / real: the dataset's gaussian_ratio and
+        # whether it is a real capture (R/...:686-689); out_dir: where mesh_init.ply / pointcloud_init.ply go (None: not written)
+        self.normal_init, self.gaussian_ratio, self.real = bool(normal_init), float(gaussian_ratio), bool(real)
+        self.normal_init_out_dir = None
+        self.last_normal_init = None  # normal_initialization's result (V, F, verts, faces, ...)
         self.last_anchor = None  # (verts, faces, fid) of the latest anchoring event
         self.stand_in_weight, self.mesh_losses = stand_in_weight, mesh_losses
         self.mesh_source, self.laplacian_loss_weight = mesh_source, laplacian_loss_weight
@@ -273,6 +288,11 @@ class Trainer:
         if dev.type == "cuda":
             self.anchor_generator = torch.Generator(device=dev)
             self.anchor_generator.manual_seed(7654321 + seed)
+        # surface samples of normal_initialization: seeded alike on every rank, like densify_generator
+        self.normal_init_generator = None
+        if dev.type == "cuda":
+            self.normal_init_generator = torch.Generator(device=dev)
+            self.normal_init_generator.manual_seed(2468013 + seed)
         self.time_interval = 1.0 / max(len(cameras), 1)
         from .deform import get_linear_noise_func
         self.smooth_term = get_linear_noise_func(lr_init=0.1, lr_final=1e-15, lr_delay_mult=0.01, max_steps=20000)
@@ -334,6 +354,26 @@ class Trainer:
         opt, ms = self.opt, self.mesh
         return (ms is not None and ms.anchor and ms.dpsr is not None and iteration >= opt.dpsr_iter and iteration > opt.anchor_iter
                 and iteration % opt.anchor_interval == 0 and opt.use_anchor > 0)
+
+    def normal_init_due(self, iteration):
+        """R/train.py:242: this iteration enters the mesh phase (MeshPhase(normal_init=True))."""
+        ms = self.mesh
+        return ms is not None and ms.normal_init and iteration == self.opt.dpsr_iter
+
+    def normal_init_step(self, d_xyz, d_rotation, d_scaling):
+        """normal_initialization with this iteration's deformation (R/train.py:242-246).  Every rank runs the chain, so the generators
+        stay in lockstep; rank 0's result is then broadcast (the ranks' frames, hence their d_xyz, differ)."""
+        from .normal_init import normal_initialization
+        g, ms = self.g, self.mesh
+        det = lambda v: v.detach() if torch.is_tensor(v) else v
+        ms.last_normal_init = normal_initialization(
+            g, self.deform, det(d_xyz), det(d_rotation), det(d_scaling), opt=self.opt, gaussian_ratio=ms.gaussian_ratio, real=ms.real,
+            generator=self.normal_init_generator, out_dir=ms.normal_init_out_dir if self.rank == 0 else None, diffmc=ms.diffmc)
+        self._area_check = ms.last_normal_init["area_check"]  # inspected at the start of the next step(): no wait here
+        if self.world > 1:
+            g.gaussian_center, g.gaussian_scale = g.gaussian_center.contiguous(), g.gaussian_scale.contiguous()
+            for t in (g._normal.data, g.gaussian_center, g.gaussian_scale, g.density_thres_param.data):
+                dist.broadcast(t, 0, group=self.group)
 
     def _shared_mesh(self, verts, faces, fid):
         """Rank 0's (verts, faces, fid), sizes first, on every rank."""
@@ -479,6 +519,11 @@ class Trainer:
                 back = self.deform_back.step(deformed_xyz.detach(), t_back)
                 cycle = (S.l1_loss(-back[0], d_xyz) + S.l1_loss(-back[1], d_rotation) + S.l1_loss(-back[2], d_scaling)) / 3.0
                 losses["cycle_loss"] = cycle
+        if self.normal_init_due(iteration):
+            if delta is not None:  # the columns glue.py reads as d_xyz / d_rotation / d_scaling
+                self.normal_init_step(delta[:, :3], delta[:, 3:7], delta[:, 7:10])
+            else:
+                self.normal_init_step(d_xyz, d_rotation, d_scaling)
         if self.mesh is not None and iteration >= opt.dpsr_iter:
             self.mesh_terms(cam, iteration, losses, pkg, delta if delta is not None else None,
                             None if delta is not None else (d_xyz if iteration >= opt.warm_up else None), time_input, t_back)
@@ -565,6 +610,9 @@ class Trainer:
 
     def step(self, iteration):
         g = self.g
+        check, self._area_check = getattr(self, "_area_check", None), None
+        if check is not None:  # the surface normal_initialization sampled last iteration had no area: its normals are all zero
+            check()
         g.update_learning_rate(iteration)
         self.deform.update_learning_rate(iteration)
         self.deform_back.update_learning_rate(iteration)
@@ -581,8 +629,9 @@ class Trainer:
         # on the device, so its gradients are discarded and the frame is rendered again with the raised capacity.  (With the
         # Gaussian bucket's early all-reduce armed the check stays inside the forward call: a discarded backward must not have
         # started a collective the other ranks do not repeat.)
-        # (an anchoring iteration is never redone: its plan draws random numbers and, with several ranks, broadcasts)
-        anchoring = self.anchor_due(iteration)
+        # (an anchoring iteration is never redone: its plan draws random numbers and, with several ranks, broadcasts; nor is the
+        # iteration that enters the mesh phase, for the same reasons)
+        anchoring = self.anchor_due(iteration) or self.normal_init_due(iteration)
         defer = _RZ.SYNC_FREE and not (self.world > 1 and self._early is not None) and not anchoring
         for _attempt in range(4):
             if self.pack:

@@ -55,7 +55,7 @@ extern "C" {
  *      dgm_mlp_set_gemm knows modes 4 and 5.
  *      Every entry point of 4 is unchanged.
  *      Later additions that leave every existing entry point and layout unchanged keep the number: dgm_mc_* (marching cubes),
- *      dgm_tri_* (mesh rasterizer), dgm_anchor_* (Gaussian-mesh anchoring). */
+ *      dgm_tri_* (mesh rasterizer), dgm_anchor_* (Gaussian-mesh anchoring), dgm_ninit_* (entering the mesh phase). */
 #define DGM_ABI_VERSION 5
 
 /* Allocator callback: must return a device pointer to at least `bytes` bytes (128-byte aligned),
@@ -498,6 +498,30 @@ int dgm_anchor_nn(int Nq, int Nt, const float* queries, const float* targets, fl
 size_t dgm_anchor_classify_scratch_bytes(int P, int F);
 int dgm_anchor_classify(int P, int F, const int* face_of, char* scratch, int* counts, int* offsets, int* lists, int* members, int* rank,
                         int* totals, void* stream);
+
+/* ---- entering the mesh phase (csrc/normal_init.hip) ------------------------------------------------------------------------------
+ * The device side of update_scale_center and normal_initialization (dgmesh/scene/gaussian_model_dpsr_dynamic_anchor.py:93-120,
+ * 684-734).  Every buffer is device memory; nothing is read back.
+ *   dgm_ninit_bbox: out6 = (min x, min y, min z, max x, max y, max z) of the P rows xyz + d_xyz (one fp32 addition; d_xyz may be
+ *       NULL = zero), in one launch.  Exact, with -0 ordered below +0, hence independent of the reduction order (the sign of a
+ *       zero extremum may differ from torch.aminmax's); a NaN coordinate makes both extrema of its axis NaN.  P >= 1.  scratch: dgm_ninit_bbox_scratch_bytes() bytes that are ZERO before the first call; every call leaves
+ *       them ready for the next one on the same stream.
+ *   dgm_ninit_face_areas: area[f] = 0.5 |cross(v1 - v0, v2 - v0)| (fp32, no FMA); 0 for a face with an index outside [0, V) and
+ *       for a non-finite result.
+ *   dgm_ninit_area_scan: cum[i] = area[0] + ... + area[i] in fp64 over a fixed partition (tiles of 4096 faces, 16 per thread;
+ *       thread totals in thread order, tile totals in tile order): non-decreasing exactly, bit-reproducible.
+ *       scratch: dgm_ninit_scan_scratch_bytes(F) bytes.
+ *   dgm_ninit_sample: for each of `count` draws u (count, 3) in [0, 1): pick = (double)u0 * cum[F - 1]; face_index = the smallest
+ *       i with cum[i] >= pick and cum[i] > 0 (numpy searchsorted side="left"; a face of area 0 is never chosen); if u1 + u2 > 1
+ *       both become 1 - u; points = v0 + (u1 (v1 - v0) + u2 (v2 - v0)) (fp32, no FMA).  cum[F - 1] == 0: face_index = -1 and NaN
+ *       points.  F >= 1. */
+size_t dgm_ninit_bbox_scratch_bytes(void);
+int dgm_ninit_bbox(int P, const float* xyz, const float* d_xyz, char* scratch, float* out6, void* stream);
+int dgm_ninit_face_areas(int V, int F, const float* verts, const int* faces, float* area, void* stream);
+size_t dgm_ninit_scan_scratch_bytes(int F);
+int dgm_ninit_area_scan(int F, const float* area, char* scratch, double* cum, void* stream);
+int dgm_ninit_sample(int V, int F, int count, const float* verts, const int* faces, const double* cum, const float* u, float* points,
+                     int* face_index, void* stream);
 
 #ifdef __cplusplus
 }
