@@ -135,8 +135,10 @@ def load_gaussians(path, max_sh_degree=3):
 # binary_little_endian: `element vertex V` with float x y z, `element face F` with `property list uchar int vertex_indices`, the
 # layout MeshLab, trimesh and Open3D read.  (A separate pair from write_ply / read_ply: the checkpoint format has no list
 # properties and read_ply keeps refusing them.)
-def write_mesh_ply(path, verts, faces):
-    """verts (V, 3) float, faces (F, 3) int (numpy arrays or tensors on any device)."""
+def write_mesh_ply(path, verts, faces, vertex_colors=None):
+    """verts (V, 3) float, faces (F, 3) int (numpy arrays or tensors on any device).  vertex_colors: (V, 3) floats in [0, 1]; the
+    vertex element then gains `uchar red green blue alpha`, the layout trimesh writes, quantised as testing() does
+    (R/train.py:730-731: clip(c * 255, 0, 255) truncated) with alpha 255."""
     as_np = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
     v = np.ascontiguousarray(as_np(verts), dtype="<f4").reshape(-1, 3)
     f = np.asarray(as_np(faces)).reshape(-1, 3)
@@ -144,8 +146,19 @@ def write_mesh_ply(path, verts, faces):
         raise ValueError("write_mesh_ply: face index out of range")
     rec = np.empty(len(f), dtype=[("n", "u1"), ("idx", "<i4", (3,))])
     rec["n"], rec["idx"] = 3, f
+    colour_props = []
+    if vertex_colors is not None:
+        c = np.asarray(as_np(vertex_colors)).reshape(-1, 3)
+        if len(c) != len(v):
+            raise ValueError(f"write_mesh_ply: {len(v)} vertices but {len(c)} colours")
+        vc = np.empty(len(v), dtype=[("xyz", "<f4", (3,)), ("rgba", "u1", (4,))])
+        vc["xyz"] = v
+        vc["rgba"][:, :3] = np.clip(c * 255, 0, 255).astype(np.uint8)
+        vc["rgba"][:, 3] = 255
+        v = vc
+        colour_props = [f"property uchar {k}" for k in ("red", "green", "blue", "alpha")]
     head = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}", "property float x", "property float y",
-            "property float z", f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
+            "property float z"] + colour_props + [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "wb") as fh:
         fh.write(("\n".join(head) + "\n").encode("ascii"))
@@ -153,8 +166,9 @@ def write_mesh_ply(path, verts, faces):
         fh.write(rec.tobytes())
 
 
-def read_mesh_ply(path):
-    """-> verts (V, 3) float32, faces (F, 3) int32 of a binary little-endian triangle-mesh PLY as write_mesh_ply writes it."""
+def read_mesh_ply(path, return_colors=False):
+    """-> verts (V, 3) float32, faces (F, 3) int32 of a binary little-endian triangle-mesh PLY as write_mesh_ply writes it; with
+    return_colors also the (V, 4) uint8 red green blue alpha of the vertices, or None when the file has none."""
     with open(path, "rb") as fh:
         data = fh.read()
     end = data.index(b"\n", data.index(b"end_header")) + 1
@@ -182,7 +196,12 @@ def read_mesh_ply(path):
     f = np.frombuffer(data, dtype=[("n", "u1"), ("idx", "<i4", (3,))], count=nf, offset=off)
     if nf and (f["n"] != 3).any():
         raise ValueError(f"{path}: only triangles are supported")
-    return verts, f["idx"].astype(np.int32).reshape(-1, 3)
+    faces = f["idx"].astype(np.int32).reshape(-1, 3)
+    if not return_colors:
+        return verts, faces
+    rgba = ("red", "green", "blue", "alpha")
+    colors = np.stack([v[k] for k in rgba], 1).astype(np.uint8) if all(k in vdt.names for k in rgba) else None
+    return verts, faces, colors
 
 
 # ---- point clouds with normals (pointcloud_init.ply of normal_initialization, R/scene/gaussian_model_dpsr_dynamic_anchor.py:722-729) --

@@ -55,7 +55,8 @@ extern "C" {
  *      dgm_mlp_set_gemm knows modes 4 and 5.
  *      Every entry point of 4 is unchanged.
  *      Later additions that leave every existing entry point and layout unchanged keep the number: dgm_mc_* (marching cubes),
- *      dgm_tri_* (mesh rasterizer), dgm_anchor_* (Gaussian-mesh anchoring), dgm_ninit_* (entering the mesh phase). */
+ *      dgm_tri_* (mesh rasterizer), dgm_anchor_* (Gaussian-mesh anchoring), dgm_ninit_* (entering the mesh phase),
+ *      dgm_image_metrics* (test-view metrics). */
 #define DGM_ABI_VERSION 5
 
 /* Allocator callback: must return a device pointer to at least `bytes` bytes (128-byte aligned),
@@ -312,6 +313,28 @@ int dgm_image_loss_forward(const float* image, const float* gt, int channels, in
 /* grad_out: device scalar dL/dloss; d_image (channels, H, W) is fully written. */
 int dgm_image_loss_backward(const float* image, const float* gt, int channels, int H, int W, float lambda_dssim,
                             const char* workspace, const float* grad_out, float* d_image, void* stream);
+
+/* ---- test-view image metrics (csrc/metrics.hip) ------------------------------------------------------- */
+
+/* MSE, PSNR, SSIM and MS-SSIM of B images against ONE target, as testing() (dgmesh/train.py:559-761) reports them; nothing is read
+ * back.  images: (B, C, H, W) fp32 device; gt: (C, H, W) fp32 device; data_range L > 0; levels is 1 or 5.
+ * out: (B, 4) DOUBLES on the device = {mse, psnr, ssim, ms_ssim}:
+ *   mse     mean squared error over all channels and pixels;  psnr = -10 log10(mse)  (get_psnr, dgmesh/utils/image_utils.py:24-28);
+ *   ssim    rgb_ssim of dgmesh/utils/metric_utils.py:26-79: 11-tap window exp(-(i-5)^2 / (2 1.5^2)) normalised to sum 1, separable,
+ *           "valid" (the map of an H x W plane is (H-10) x (W-10)), C1 = (0.01 L)^2, C2 = (0.03 L)^2, variances clipped at 0,
+ *           |sigma01| bounded by sqrt(sigma00 sigma11), mean over pixels and channels;
+ *   ms_ssim (levels == 5; NaN otherwise) the defaults of the pytorch_msssim package in this project's own words: weights
+ *           (0.0448, 0.2856, 0.3001, 0.2363, 0.1333); per level and channel, no clipping, cs = mean((2 sigma01 + C2) /
+ *           (sigma00 + sigma11 + C2)) and ssim_l = mean(((2 mu0 mu1 + C1) / (mu0^2 + mu1^2 + C1)) cs_map); between levels both images
+ *           are 2x2 average-pooled with stride 2, an odd side zero-padded by one on BOTH ends, divisor 4; per channel
+ *           prod_{l<4} relu(cs_l)^w_l * relu(ssim_4)^w_4; mean over channels.
+ * levels == 5 needs min(H, W) > 160, levels == 1 min(H, W) >= 11: otherwise the call fails and workspace_bytes returns 0.
+ * Inputs are fp32, all arithmetic is fp64; sums run over a fixed partition in a fixed order (no atomics), so the results are
+ * bit-reproducible and row b does not depend on B.  workspace: dgm_image_metrics_workspace_bytes(...) bytes, caller-owned, no
+ * initial state. */
+size_t dgm_image_metrics_workspace_bytes(int B, int C, int H, int W, int levels);
+int dgm_image_metrics(const float* images, const float* gt, int B, int C, int H, int W, float data_range, int levels, char* workspace,
+                      double* out, void* stream);
 
 /* ---- per-Gaussian glue of the train step ------------------------------------------------------------------ */
 
