@@ -117,6 +117,11 @@ SYMBOLS = {
     "dgm_ninit_scan_scratch_bytes": (_c.c_size_t, [_i]),
     "dgm_ninit_area_scan": (_i, [_i, _vp, _vp, _vp, _vp]),
     "dgm_ninit_sample": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_vertex_normals": (_i, [_i, _i, _vp, _vp, _vp, _vp]),
+    "dgm_mesh_shade": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_point_splat_scratch_bytes": (_c.c_size_t, [_i, _i]),
+    "dgm_point_splat": (_i, [_i, _i, _i, _vp, _vp, _i, _c.POINTER(_f), _vp, _vp, _vp]),
+    "dgm_compose_frame": (_i, [_i, _c.POINTER(_vp), _c.POINTER(_i), _i, _i, _i, _vp, _vp]),
     "dgm_mlp_set_gemm": (_i, [_i]),
     "dgm_timenet_forward": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "dgm_timenet_backward": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

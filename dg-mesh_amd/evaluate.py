@@ -61,17 +61,23 @@ def image_metrics(images, gt, data_range=1.0, ms_ssim=True):
     return {k: out[:, i] for i, k in enumerate(COLUMNS) if ms_ssim or k != "ms_ssim"}
 
 
-def _mesh_view(mesh, gaussians, deform_back, d_xyz, d_normal, cam, white_background):
-    """mesh_renderer of R/utils/renderer.py:124-230 without its losses: the DiffMC surface of the deformed Gaussians, the vertex
-    colours (deform_back + appearance at the noise-free fid) and the mesh image."""
-    from .mesh_raster import render_mesh
+def mesh_and_colors(mesh, gaussians, deform_back, d_xyz, d_normal, fid, who="testing"):
+    """mesh_renderer of R/utils/renderer.py:124-230 up to its rendering: the DiffMC surface of the deformed Gaussians and the vertex
+    colours (deform_back + appearance at the noise-free `fid`, a one-element tensor): (verts, faces, vtx_color).  Shared by
+    testing() and the drivers of visualize.py."""
     verts, faces = mesh.surface(gaussians, mesh.psr(gaussians, d_xyz, d_normal))
     V = verts.shape[0]
     if V == 0:
-        raise RuntimeError("testing: the DPSR field has no surface at the density threshold (DiffMC returned no vertices)")
-    t_v = cam.fid.reshape(1, 1).expand(V, -1)
+        raise RuntimeError(f"{who}: the DPSR field has no surface at the density threshold (DiffMC returned no vertices)")
+    t_v = fid.reshape(1, 1).expand(V, -1)
     back_v = deform_back.step(verts, t_v)[0]
-    vtx_color = mesh.appearance.step(verts + back_v, t_v)
+    return verts, faces, mesh.appearance.step(verts + back_v, t_v)
+
+
+def _mesh_view(mesh, gaussians, deform_back, d_xyz, d_normal, cam, white_background):
+    """mesh_and_colors and the mesh image."""
+    from .mesh_raster import render_mesh
+    verts, faces, vtx_color = mesh_and_colors(mesh, gaussians, deform_back, d_xyz, d_normal, cam.fid)
     return render_mesh(None, verts, faces, vtx_color, cam, whitebackground=white_background), verts, faces, vtx_color
 
 

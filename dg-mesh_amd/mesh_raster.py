@@ -222,14 +222,20 @@ def _resolution(cam, resolution):
     return (int(cam.image_height), int(cam.image_width)) if resolution is None else tuple(int(r) for r in resolution)
 
 
-def render_mask_and_mesh(glctx, verts, faces, vtx_color, cam, resolution=None, whitebackground=False):
+def render_mask_and_mesh(glctx, verts, faces, vtx_color, cam, resolution=None, whitebackground=False, rast=None):
     """render_mask and render_mesh of R/utils/renderer.py:33-121 from one rasterize and one 4-channel interpolate / antialias
     (colour + ones; antialias is linear per channel, so this equals the reference's separate calls): (mask (H, W, 1), image
-    (3, H, W)).  verts (V, 3) world space, faces (F, 3) int32, vtx_color (V, 3), cam: a TorchCamera."""
+    (3, H, W)).  verts (V, 3) world space, faces (F, 3) int32, vtx_color (V, 3), cam: a TorchCamera.  rast: the (1, H, W, 4) result
+    of rasterize(clip_positions(cam, verts), faces, (H, W)) when the caller already has it (visualize.py shades the same buffer)."""
     H, W = _resolution(cam, resolution)
     pos = clip_positions(cam, verts)
     faces = faces.contiguous()
-    rast, _ = rasterize(glctx, pos, faces, (H, W))
+    if rast is None:
+        rast, _ = rasterize(glctx, pos, faces, (H, W))
+    else:
+        _check_rast("render_mesh", rast, pos.device)
+        if tuple(rast.shape[1:3]) != (H, W):
+            raise RuntimeError(f"render_mesh: rast {tuple(rast.shape)} does not match the resolution {(H, W)}")
     attr = torch.cat([vtx_color, torch.ones_like(vtx_color[:, :1])], dim=1).contiguous()
     col, _ = interpolate(attr, rast, faces)
     col = antialias(col, rast, pos, faces)[0]
@@ -250,6 +256,6 @@ def render_mask(glctx, verts, faces, cam, resolution=None):
     return antialias(m, rast, pos, faces)[0]
 
 
-def render_mesh(glctx, verts, faces, vtx_color, cam, resolution=None, whitebackground=False):
+def render_mesh(glctx, verts, faces, vtx_color, cam, resolution=None, whitebackground=False, rast=None):
     """R/utils/renderer.py:69-121: the antialiased vertex colour, background where the mask is 0, clamped to [0, 1], (3, H, W)."""
-    return render_mask_and_mesh(glctx, verts, faces, vtx_color, cam, resolution, whitebackground)[1]
+    return render_mask_and_mesh(glctx, verts, faces, vtx_color, cam, resolution, whitebackground, rast)[1]

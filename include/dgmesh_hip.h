@@ -56,7 +56,8 @@ extern "C" {
  *      Every entry point of 4 is unchanged.
  *      Later additions that leave every existing entry point and layout unchanged keep the number: dgm_mc_* (marching cubes),
  *      dgm_tri_* (mesh rasterizer), dgm_anchor_* (Gaussian-mesh anchoring), dgm_ninit_* (entering the mesh phase),
- *      dgm_image_metrics* (test-view metrics). */
+ *      dgm_image_metrics* (test-view metrics), dgm_vertex_normals / dgm_mesh_shade / dgm_point_splat* / dgm_compose_frame
+ *      (rendering a checkpoint). */
 #define DGM_ABI_VERSION 5
 
 /* Allocator callback: must return a device pointer to at least `bytes` bytes (128-byte aligned),
@@ -545,6 +546,50 @@ size_t dgm_ninit_scan_scratch_bytes(int F);
 int dgm_ninit_area_scan(int F, const float* area, char* scratch, double* cum, void* stream);
 int dgm_ninit_sample(int V, int F, int count, const float* verts, const int* faces, const double* cum, const float* u, float* points,
                      int* face_index, void* stream);
+
+/* ---- rendering a checkpoint (csrc/visualize.hip) --------------------------------------------------------------------------------
+ * The device side of mesh_shape_renderer / pointcloud_renderer (dgmesh/utils/renderer.py:236-374) and of the frame composition of
+ * render_test.py / render_trajectory.py.  Every pointer is device memory unless it says host; nothing is read back.  fp32, no FMA.
+ *   dgm_vertex_normals: normals (V, 3) (zeroed by the call) = the area-weighted vertex normals: cross(v1 - v0, v2 - v0) of every face
+ *       added to its three vertices, each vertex then divided by its length; a length below 1e-6 gives (0, 0, 0).  A face with an index
+ *       outside [0, V) is skipped.  The sums are fp32 atomics: the result agrees to rounding, not bit for bit, run to run.
+ *   dgm_mesh_shade: a deferred hard-Phong pass over the mesh rasterizer's rast (H, W, 4) = (u, v, z/w, id + 1).  Per covered pixel:
+ *       p and n interpolated with (u, v, 1 - u - v) from verts and normals, n scaled by normal_sign and renormalised (length < 1e-6:
+ *       zero); one directional light l (unit vector towards the light): diffuse = max(n.l, 0), r = 2 (n.l) n - l,
+ *       view = normalize(camera_center - p), spec = n.l > 0 ? max(view.r, 0)^shininess : 0;
+ *       image (H, W, 3) = clamp((ambient + diffuse_k * diffuse) * base_color + specular_k * spec, 0, 1); background where id is 0 (or
+ *       names no valid face).  params: ONE dgm_shade_params in device memory (the light may have been computed on the device).
+ *   dgm_point_splat: every point of pos_clip (N, 4) with w > 0 and finite coordinates lands on pixel floor(s), s = ((x/w + 1) W/2,
+ *       (y/w + 1) H/2) (the mesh rasterizer's mapping), and covers the size x size square of pixels centred there, clipped to the image
+ *       (size odd, 1..15).  Per pixel the smallest z/w wins, ties to the lower point id: one 64-bit atomicMin of
+ *       (ordered z/w bits) << 32 | id.  image (H, W, 3) = the winner's colour -- colors (N, 3), or, when colors is NULL,
+ *       bg_color6[3..5] -- and bg_color6[0..2] elsewhere; bg_color6 is a HOST array of six floats.  Bit-reproducible.
+ *       scratch: dgm_point_splat_scratch_bytes(H, W) bytes (0 for invalid sizes); after the call its first H W uint64 hold the winning
+ *       keys (all ones: empty; low 32 bits: the point id).
+ *   dgm_compose_frame: n_panels (1..4) fp32 panels of H x W pixels, panels[k] (a HOST array of device pointers) laid out (3, H, W)
+ *       when layouts[k] (HOST) is 0 and (H, W, 3) when it is 1, side by side into out_u8 (H/d, n_panels W/d, 3) uint8.  d = downsample
+ *       is 1 or 2 (then H and W are even): each 2x2 block averages as ((a + b) + (c + d)) * 0.25, top row first.  Then
+ *       clamp to [0, 1], times 255, truncated toward zero; NaN writes 0. */
+typedef struct dgm_shade_params {
+    float light_dir[3];      /* unit vector from the surface towards the light */
+    float ambient;
+    float camera_center[3];
+    float diffuse;           /* light diffuse x material diffuse */
+    float background[3];
+    float specular;          /* light specular x material specular */
+    float base_color[3];
+    float shininess;
+    float normal_sign;       /* +1, or -1 for a mesh wound inwards */
+    float pad[3];
+} dgm_shade_params;
+int dgm_vertex_normals(int V, int F, const float* verts, const int* faces, float* normals, void* stream);
+int dgm_mesh_shade(int V, int F, int H, int W, const float* verts, const float* normals, const int* faces, const float* rast,
+                   const dgm_shade_params* params, float* image, void* stream);
+size_t dgm_point_splat_scratch_bytes(int H, int W);
+int dgm_point_splat(int N, int H, int W, const float* pos_clip, const float* colors, int size, const float* bg_color6, char* scratch,
+                    float* image, void* stream);
+int dgm_compose_frame(int n_panels, const float* const* panels, const int* layouts, int H, int W, int downsample, unsigned char* out_u8,
+                      void* stream);
 
 #ifdef __cplusplus
 }
