@@ -122,6 +122,10 @@ SYMBOLS = {
     "dgm_point_splat_scratch_bytes": (_c.c_size_t, [_i, _i]),
     "dgm_point_splat": (_i, [_i, _i, _i, _vp, _vp, _i, _c.POINTER(_f), _vp, _vp, _vp]),
     "dgm_compose_frame": (_i, [_i, _c.POINTER(_vp), _c.POINTER(_i), _i, _i, _i, _vp, _vp]),
+    "dgm_emd_tile": (_i, [_i]),
+    "dgm_emd_parts": (_i, [_i, _i]),
+    "dgm_emd_scratch_floats": (_c.c_size_t, [_i, _i, _i]),
+    "dgm_emd_approx": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dgm_mlp_set_gemm": (_i, [_i]),
     "dgm_timenet_forward": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "dgm_timenet_backward": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

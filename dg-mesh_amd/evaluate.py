@@ -5,7 +5,8 @@
 pytorch_msssim is not vendored and not a dependency: the MS-SSIM here is this project's own statement of that package's defaults
 (11-tap sigma-1.5 window without padding, five levels with weights 0.0448, 0.2856, 0.3001, 0.2363, 0.1333, 2x2 average pooling whose
 odd sides are zero-padded on both ends, relu on each level's term, mean over channels); tests/_metrics_ref.py restates it in numpy.
-LPIPS needs network weights and is not computed; the Chamfer / EMD mesh metrics are not part of this module.
+LPIPS needs network weights and is not computed; the Chamfer / EMD metrics of exported meshes against ground truth (the
+reference's mesh_evaluation.py) are in mesh_eval.py.
 
 The reference copies four images to the host and makes six host round trips per view.  Here one dgm_image_metrics call per view
 scores the Gaussian image and the mesh image against the target and writes a row of a device-side table that is read back once,

@@ -591,6 +591,30 @@ int dgm_point_splat(int N, int H, int W, const float* pos_clip, const float* col
 int dgm_compose_frame(int n_panels, const float* const* panels, const int* layouts, int H, int W, int downsample, unsigned char* out_u8,
                       void* stream);
 
+/* ---- mesh evaluation: approximate earth mover's distance (csrc/emd.hip) -------------------------------------------------------------
+ * Replaces approxmatchkernel + matchcostkernel (dgmesh/metrics/pytorch_structural_losses/src/approxmatch.cu:3-224), the match cost
+ * behind the EMD column of dgmesh/mesh_evaluation.py.  xyz1 (b, n, 3), xyz2 (b, m, 3) fp32; every buffer is device memory, nothing
+ * is allocated and nothing is read back.  No n x m array is formed: sum(match * dist) is accumulated while the match is computed.
+ * The iteration, with its integer-division mass rule (multiL, multiR) = (1, n / m) or (m / n, 1) and its nine levels -4^7 .. -4^-1,
+ * is stated at the top of csrc/emd.hip.  No atomics: two calls on the same input return the same bits, and a batch returns the bits
+ * its elements return alone.
+ *   dgm_emd_tile: constants of the launch structure: which = 0 the rows per workgroup, 1 the columns per LDS tile, 2 the number of
+ *       workgroups a sweep aims for per batch element, 3 the number of levels; 0 for any other `which`.
+ *   dgm_emd_parts: the number of column parts of a sweep over `rows` rows and `cols` columns: with rt = ceil(rows / tile 0) and
+ *       ct = ceil(cols / tile 1), want = min(ct, ceil(tile 2 / rt)), each part takes ceil(ct / want) column tiles.  0 for sizes
+ *       outside [1, 2^28].
+ *   dgm_emd_scratch_floats: the caller-owned scratch of one call, in floats: five vectors of b n or b m floats and the partial
+ *       sums, b max(2 n parts(n, m), m parts(m, n)) floats; 0 for invalid sizes.  Its contents on entry do not matter.
+ *   dgm_emd_approx: cost (b) = sum over the nine levels of sum w[k,l] sqrt(d2[k,l]) (not divided by n); residual (b, 2), unless
+ *       NULL, = (sum remainL, sum remainR) after the last level, the mass that was not transported.  1 <= b <= 65535,
+ *       1 <= n, m <= 2^28: row, column and tile indices are int, which that cap keeps far from overflow; every buffer offset
+ *       (b n 3, b parts n) is 64-bit. */
+int dgm_emd_tile(int which);
+int dgm_emd_parts(int rows, int cols);
+size_t dgm_emd_scratch_floats(int b, int n, int m);
+int dgm_emd_approx(int b, int n, int m, const float* xyz1, const float* xyz2, float* scratch, float* cost, float* residual,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
