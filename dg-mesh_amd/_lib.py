@@ -126,6 +126,8 @@ SYMBOLS = {
     "dgm_emd_parts": (_i, [_i, _i]),
     "dgm_emd_scratch_floats": (_c.c_size_t, [_i, _i, _i]),
     "dgm_emd_approx": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_png_unfilter": (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
+    "dgm_image_ingest": (_i, [_i, _i, _i, _i, _vp, _c.POINTER(_f), _vp, _vp, _vp]),
     "dgm_mlp_set_gemm": (_i, [_i]),
     "dgm_timenet_forward": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "dgm_timenet_backward": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -5,8 +5,8 @@
                      :679-682 (add_densification_stats)
   render()        <- R/gaussian_renderer/__init__.py:32-119 (same signature, same returned dict)
   l1_loss / ssim  <- R/utils/loss_utils.py:18-19, 32-76
-(R/ = /root/reference/dgmesh/.)  Densification / pruning: densify.py.  Mesh branch (DiffMC / nvdiffrast) and dataset
-readers are out of scope.
+(R/ = /root/reference/dgmesh/.)  Densification / pruning: densify.py.  Scenes on disk (Scene, the Blender / D-NeRF reader):
+dataset.py; the mesh branch: trainer.py.
 """
 import math
 from math import exp

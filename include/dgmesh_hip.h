@@ -57,7 +57,7 @@ extern "C" {
  *      Later additions that leave every existing entry point and layout unchanged keep the number: dgm_mc_* (marching cubes),
  *      dgm_tri_* (mesh rasterizer), dgm_anchor_* (Gaussian-mesh anchoring), dgm_ninit_* (entering the mesh phase),
  *      dgm_image_metrics* (test-view metrics), dgm_vertex_normals / dgm_mesh_shade / dgm_point_splat* / dgm_compose_frame
- *      (rendering a checkpoint). */
+ *      (rendering a checkpoint), dgm_emd_* (mesh evaluation), dgm_png_unfilter / dgm_image_ingest (reading a dataset). */
 #define DGM_ABI_VERSION 5
 
 /* Allocator callback: must return a device pointer to at least `bytes` bytes (128-byte aligned),
@@ -614,6 +614,22 @@ int dgm_emd_parts(int rows, int cols);
 size_t dgm_emd_scratch_floats(int b, int n, int m);
 int dgm_emd_approx(int b, int n, int m, const float* xyz1, const float* xyz2, float* scratch, float* cost, float* residual,
                    void* stream);
+
+/* ---- dataset ingest: PNG unfiltering and compositing over the background (csrc/ingest.hip) -------------------------------------------
+ * Replaces PIL's decoder and the numpy compositing of readCamerasFromTransforms + PILtoTorch (dgmesh/scene/dataset_readers.py:288-302,
+ * dgmesh/utils/general_utils.py:23-29).  Every buffer but bg3 is device memory; nothing is allocated and nothing is read back.
+ *   dgm_png_unfilter: `filtered` holds B inflated IDAT streams of 8-bit, non-interlaced images of one W, H and channels (3: colour type
+ *       2, 4: colour type 6), back to back: each H rows of 1 + W channels bytes, the first byte of a row its filter type 0..4 (None,
+ *       Sub, Up, Average with floor((a + b) / 2), Paeth with the specification's tie order; arithmetic mod 256 per byte, neighbours
+ *       `channels` bytes apart).  out (B, H, W, channels) uint8, 4-byte aligned.  A filter type above 4 is read as 0: the caller checks
+ *       the type bytes before the upload.  One workgroup per image, one lane per row, rows skewed by one pixel; the trip counts are
+ *       uniform and no thread waits on memory.  1 <= W, H <= 2^24; offsets are 64-bit.
+ *   dgm_image_ingest: in (B, H, W, C) uint8, C 3 or 4 (C = 3: alpha 255); bg3 a HOST array of three floats.  In fp64 and in this
+ *       order, without contraction: n = byte / 255.0, v = (n_c n_a + bg (1 - n_a)) 255.0, q = v truncated to a byte; then
+ *       image (B, 3, H, W) = (float)q / 255.0f correctly rounded, and mask (B, H, W, 1) = (float)n_a.  1 <= B <= 65535.  image and
+ *       mask are 4-byte aligned; `in` is 4-byte aligned for C = 4 and may start at any byte for C = 3. */
+int dgm_png_unfilter(int B, int W, int H, int channels, const unsigned char* filtered, unsigned char* out, void* stream);
+int dgm_image_ingest(int B, int H, int W, int C, const unsigned char* in, const float* bg3, float* image, float* mask, void* stream);
 
 #ifdef __cplusplus
 }
