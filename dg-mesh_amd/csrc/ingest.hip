@@ -12,6 +12,7 @@
 //                    loaded during the step before.  Images taller than 1024 rows are
 //                    walked in bands by the same workgroup: row 0 of a later band reads `up` from the finished row above in `out`.
 //   ingest kernel  : four pixels per thread (16 bytes in, 4 x 16 bytes out), fp64 arithmetic in the reference's order.
+//   composite kernel: the same bytes before the division, as (R, G, B, file alpha) words: the input of a `resolution` resize.
 //
 // Built with -ffp-contract=off and correctly rounded fp32 division: (n_c n_a + bg (1 - n_a)) 255 truncates to a different byte than
 // any contracted or integer form for some (colour, alpha) pairs.
@@ -104,14 +105,33 @@ __global__ __launch_bounds__(UF_ROWS) void png_unfilter_kernel(int W, int H, con
     }
 }
 
-// (n_c n_a + bg (1 - n_a)) 255 in fp64, truncated to a byte; then byte / 255 in fp32
-__device__ __forceinline__ float composite(unsigned c, double na, double bg) {
+// (n_c n_a + bg (1 - n_a)) 255 in fp64, truncated to a byte
+__device__ __forceinline__ unsigned composite_byte(unsigned c, double na, double bg) {
     const double nc = (double)c / 255.0;
     const double t0 = nc * na;
     const double t1 = bg * (1.0 - na);
     const double v = (t0 + t1) * 255.0;
-    const unsigned q = (unsigned)(int)v & 255u;
-    return (float)q / 255.0f;
+    return (unsigned)(int)v & 255u;
+}
+
+// then byte / 255 in fp32
+__device__ __forceinline__ float composite(unsigned c, double na, double bg) {
+    return (float)composite_byte(c, na, bg) / 255.0f;
+}
+
+// four pixels of a (.., C) byte image as RGBA words (alpha 255 for C = 3); src may start at any byte for C = 3
+template <int C>
+__device__ __forceinline__ void load4_rgba(const unsigned char* src, unsigned px[4]) {
+    if (C == 4) {
+        const dgm_u4u v = *(const dgm_u4u*)src;
+        px[0] = v.x, px[1] = v.y, px[2] = v.z, px[3] = v.w;
+    } else {
+        const unsigned w0 = *(const dgm_u32b*)src, w1 = *(const dgm_u32b*)(src + 4), w2 = *(const dgm_u32b*)(src + 8);
+        px[0] = (w0 & 0xffffffu) | 0xff000000u;
+        px[1] = (w0 >> 24) | ((w1 & 0xffffu) << 8) | 0xff000000u;
+        px[2] = (w1 >> 16) | ((w2 & 0xffu) << 16) | 0xff000000u;
+        px[3] = (w2 >> 8) | 0xff000000u;
+    }
 }
 
 template <int C>
@@ -126,16 +146,7 @@ __global__ __launch_bounds__(256) void image_ingest_kernel(long long HW, const u
     const double bg[3] = {bg0, bg1, bg2};
     if (n0 + 4 <= HW) {
         unsigned px[4];
-        if (C == 4) {
-            const dgm_u4u v = *(const dgm_u4u*)src;
-            px[0] = v.x, px[1] = v.y, px[2] = v.z, px[3] = v.w;
-        } else {
-            const unsigned w0 = *(const dgm_u32b*)src, w1 = *(const dgm_u32b*)(src + 4), w2 = *(const dgm_u32b*)(src + 8);
-            px[0] = (w0 & 0xffffffu) | 0xff000000u;
-            px[1] = (w0 >> 24) | ((w1 & 0xffffu) << 8) | 0xff000000u;
-            px[2] = (w1 >> 16) | ((w2 & 0xffu) << 16) | 0xff000000u;
-            px[3] = (w2 >> 8) | 0xff000000u;
-        }
+        load4_rgba<C>(src, px);
         double na[4];
         dgm_f4u m;
 #pragma unroll
@@ -157,6 +168,41 @@ __global__ __launch_bounds__(256) void image_ingest_kernel(long long HW, const u
             const double na = (double)(C == 4 ? (unsigned)p[3] : 255u) / 255.0;
             msk[k] = (float)na;
             for (int c = 0; c < 3; c++) img[(size_t)c * HW + k] = composite((unsigned)p[c], na, bg[c]);
+        }
+    }
+}
+
+// the composited bytes themselves, with the file's alpha beside them: what the `resolution` resize takes (csrc/resample.hip)
+template <int C>
+__global__ __launch_bounds__(256) void image_composite_kernel(long long HW, const unsigned char* __restrict__ in, double bg0, double bg1,
+                                                              double bg2, unsigned char* __restrict__ out) {
+    const long long n0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (n0 >= HW) return;
+    const size_t b = blockIdx.y;
+    const unsigned char* src = in + (b * (size_t)HW + (size_t)n0) * C;
+    unsigned* dst = (unsigned*)out + b * (size_t)HW + (size_t)n0;
+    const double bg[3] = {bg0, bg1, bg2};
+    if (n0 + 4 <= HW) {
+        unsigned px[4];
+        load4_rgba<C>(src, px);
+        dgm_u4u o;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const double na = (double)(px[k] >> 24) / 255.0;
+            unsigned w = px[k] & 0xff000000u;
+#pragma unroll
+            for (int c = 0; c < 3; c++) w |= composite_byte((px[k] >> (8 * c)) & 255u, na, bg[c]) << (8 * c);
+            o[k] = w;
+        }
+        *(dgm_u4u*)dst = o;
+    } else {
+        for (long long k = 0; n0 + k < HW; k++) {
+            const unsigned char* p = src + k * C;
+            const unsigned a = C == 4 ? (unsigned)p[3] : 255u;
+            const double na = (double)a / 255.0;
+            unsigned w = a << 24;
+            for (int c = 0; c < 3; c++) w |= composite_byte((unsigned)p[c], na, bg[c]) << (8 * c);
+            dst[k] = w;
         }
     }
 }
@@ -212,6 +258,28 @@ int dgm_image_ingest(int B, int H, int W, int C, const unsigned char* in, const 
     else
         hipLaunchKernelGGL(image_ingest_kernel<3>, grid, dim3(256), 0, st, HW, in, (double)bg3[0], (double)bg3[1], (double)bg3[2], image, mask);
     return launch_status("image_ingest");
+}
+
+int dgm_image_composite_bytes(int B, int H, int W, int C, const unsigned char* in, const float* bg3, unsigned char* out, void* stream) {
+    if (B < 1 || B > 65535 || W < 1 || H < 1 || W > (1 << 24) || H > (1 << 24) || (C != 3 && C != 4) || !in || !bg3 || !out ||
+        (C == 4 && ((uintptr_t)in & 3)) || ((uintptr_t)out & 3)) {
+        set_last_error("image_composite_bytes: bad argument (1 <= B <= 65535, 1 <= W, H <= 2^24, C 3 or 4, no null pointer, out 4-byte "
+                       "aligned, in 4-byte aligned when C is 4)");
+        return 1;
+    }
+    const long long HW = (long long)H * W;
+    const long long blocks = ((HW + 3) / 4 + 255) / 256;
+    if (blocks > 0x7fffffffLL) {
+        set_last_error("image_composite_bytes: image too large");
+        return 1;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)blocks, (unsigned)B);
+    if (C == 4)
+        hipLaunchKernelGGL(image_composite_kernel<4>, grid, dim3(256), 0, st, HW, in, (double)bg3[0], (double)bg3[1], (double)bg3[2], out);
+    else
+        hipLaunchKernelGGL(image_composite_kernel<3>, grid, dim3(256), 0, st, HW, in, (double)bg3[0], (double)bg3[1], (double)bg3[2], out);
+    return launch_status("image_composite_bytes");
 }
 
 }  // extern "C"

@@ -5,12 +5,20 @@ as the cameras, ground-truth images and initial point cloud that training needs.
                          (:93-114), fetchPly / storePly (:183-208); camera matrices as R/scene/cameras.py:54-71
   Scene               <- R/scene/__init__.py:25-141, cameraList_from_camInfos / camera_to_JSON (R/utils/camera_utils.py:23-95)
 (R/ = dgmesh/.)  The images never pass through the host as pixels: png_io.decode_pngs inflates the files on the host and undoes
-the PNG filters on the device, image_ingest composites them over the background there (csrc/ingest.hip).
+the PNG filters on the device, image_ingest composites them over the background there (csrc/ingest.hip), and `downsample` and
+`resolution` resize them there with Pillow's arithmetic (resample.py, csrc/resample.hip).
+
+The reader only reads PNG headers, so resizing is a stage of Scene._load, in the reference's order: decode; Lanczos on the file's
+bytes when `downsample` changes the size (dataset_readers.py:289; RGBA through Pillow's premultiplied path); composite; bicubic
+when `resolution` changes the size again (loadCam, R/utils/camera_utils.py:23-46); divide by 255.  CameraInfo.width, height and FoVy
+and cameras.json follow the downsampled size, the TorchCameras the final one; FoVs do not depend on `resolution`.
 
 Deviation from the reference: it swaps the two field-of-view names (FovY = fovx; FovX = fovy, dataset_readers.py:304-306), which is
 harmless for square images and wrong otherwise.  Here FoVx is the file's camera_angle_x and FoVy follows from the aspect ratio.
-Not built: downsample != 1 and a `resolution` that would resize (PIL's Lanczos / bicubic resampling is not restated): both raise
-NotImplementedError.  Nerfies, iPhone and NeuralActor scenes have other readers in the reference; they raise by name here."""
+Under `resolution` the reference resizes the image and leaves the alpha mask at its old size, so its mask loss cannot run; here the
+alpha plane is resampled with the same bicubic filter as a fourth, non-premultiplied channel and the mask always has the image's size.
+Not built: Nerfies, iPhone and NeuralActor scenes have other readers in the reference; they raise by name here.
+read_blender_scene itself still reads at file size only (downsample=1.0); Scene applies `downsample`."""
 import ctypes
 import json
 import math
@@ -21,7 +29,7 @@ from typing import NamedTuple
 
 import numpy as np
 
-from . import png_io, synthetic
+from . import png_io, resample, synthetic
 
 ZNEAR, ZFAR = 0.01, 100.0  # R/scene/cameras.py:54-55
 DEFAULT_POINTS = 100_000
@@ -205,6 +213,35 @@ def image_ingest(pixels, background):
     return image, mask
 
 
+def image_composite_bytes(pixels, background):
+    """dgm_image_composite_bytes: image_ingest's composited bytes before the division, (B, H, W, 4) uint8 = (R, G, B over the
+    background, the file's alpha; 255 for three-channel files): what a `resolution` resize takes."""
+    import torch
+
+    from . import _lib
+    if not (torch.is_tensor(pixels) and pixels.is_cuda and pixels.dtype == torch.uint8 and pixels.dim() == 4 and pixels.shape[3] in (3, 4)):
+        raise RuntimeError("image_composite_bytes needs a (B, H, W, 3 or 4) uint8 CUDA/HIP tensor (dg-mesh_amd has no CPU path for its kernels)")
+    pixels = pixels.contiguous()
+    B, H, W, C = pixels.shape
+    out = torch.empty((B, H, W, 4), dtype=torch.uint8, device=pixels.device)
+    bg = (ctypes.c_float * 3)(*[float(v) for v in background])
+    with _lib.device_guard(pixels.device):
+        _lib.check(_lib.lib().dgm_image_composite_bytes(B, H, W, C, ctypes.c_void_p(pixels.data_ptr()), bg, ctypes.c_void_p(out.data_ptr()),
+                                                        _lib.stream_ptr()))
+    return out
+
+
+def downsampled(info, downsample):
+    """The CameraInfo after readCamerasFromTransforms' image.resize((int(W / downsample), int(H / downsample))): width, height, and
+    FoVy recomputed from the resized size; FoVx stays the file's camera_angle_x."""
+    w, h = resample.target_size_downsample(info.width, info.height, downsample)
+    if w < 1 or h < 1:
+        raise ValueError(f"Scene: downsample={downsample} leaves no pixels of {info.image_path} ({info.width} x {info.height})")
+    if (w, h) == (info.width, info.height):
+        return info
+    return info._replace(width=w, height=h, FoVy=2 * math.atan(math.tan(info.FoVx / 2) * h / w))
+
+
 def camera_to_json(uid, info):
     """camera_to_JSON (R/utils/camera_utils.py:75-95)."""
     Rt = np.zeros((4, 4))
@@ -218,7 +255,8 @@ def camera_to_json(uid, info):
 
 
 def check_resolution(resolution, infos):
-    """loadCam (R/utils/camera_utils.py:23-46) keeps the file's size for resolution 1, and for -1 up to 1600 pixels of width."""
+    """Names what loads without resampling: loadCam (R/utils/camera_utils.py:23-46) keeps the file's size for resolution 1, and
+    for -1 up to 1600 pixels of width.  (Scene resizes for every other value and does not call this.)"""
     if resolution == 1 or (resolution == -1 and all(c.width <= 1600 for c in infos)):
         return
     raise NotImplementedError(f"Scene: resolution={resolution} would resize the images (only 1, or -1 with widths <= 1600, is built)")
@@ -238,9 +276,15 @@ class Scene:
                 load_iteration = max(int(f.split("_")[-1]) for f in os.listdir(os.path.join(self.model_path, "point_cloud")))
             self.loaded_iter = load_iteration
         os.makedirs(self.model_path, exist_ok=True)
-        info = READERS[scene_type(args)](args.source_path, args.white_background, args.eval, downsample=getattr(args, "downsample", 1.0),
+        info = READERS[scene_type(args)](args.source_path, args.white_background, args.eval, downsample=1.0,
                                          model_path=self.model_path, seed=seed)
-        check_resolution(getattr(args, "resolution", -1), info.train_cameras + info.test_cameras)
+        d = float(getattr(args, "downsample", 1.0))
+        if not d > 0:
+            raise ValueError(f"Scene: downsample must be positive, got {d}")
+        if d != 1.0:  # (the reader saw the files' sizes; from here on the cameras carry the downsampled ones)
+            info = info._replace(train_cameras=[downsampled(c, d) for c in info.train_cameras],
+                                 test_cameras=[downsampled(c, d) for c in info.test_cameras])
+        self.downsample, self.resolution = d, getattr(args, "resolution", -1)
         if not self.loaded_iter:
             if info.ply_path is not None and os.path.dirname(os.path.abspath(info.ply_path)) != os.path.abspath(self.model_path):
                 with open(info.ply_path, "rb") as src, open(os.path.join(self.model_path, "input.ply"), "wb") as dst:
@@ -268,18 +312,29 @@ class Scene:
                 gaussians.create_from_pcd(pcd.points, pcd.colors, pcd.normals if np.any(pcd.normals) else None)
 
     def _load(self, infos, background, S):
-        """TorchCameras of one split; original_image / gt_alpha_mask are views into one batch per image shape."""
+        """TorchCameras of one split; original_image / gt_alpha_mask are views into one batch per image shape.  infos carry the size
+        after `downsample`; the stages are those of the module docstring."""
         if not infos:
             return []
         images, masks = [None] * len(infos), [None] * len(infos)
         for idx, pixels in png_io.decode_png_groups([c.image_path for c in infos], self.device):
-            im, mk = image_ingest(pixels, background)
+            w, h = resample.target_size_downsample(pixels.shape[2], pixels.shape[1], self.downsample)
+            if any((infos[i].width, infos[i].height) != (w, h) for i in idx):  # (the sizes the reader took from the headers)
+                raise ValueError(f"Scene: {infos[idx[0]].image_path}: size changed while loading")
+            if (w, h) != (pixels.shape[2], pixels.shape[1]):
+                pixels = resample.resize(pixels, (w, h), "lanczos")
+            final = resample.target_size_resolution(w, h, self.resolution)
+            if min(final) < 1:
+                raise ValueError(f"Scene: resolution={self.resolution} leaves no pixels of a {w} x {h} image")
+            if final == (w, h):
+                im, mk = image_ingest(pixels, background)
+            else:
+                im, mk = resample.resize(image_composite_bytes(pixels, background), final, "bicubic", premultiplied=False, out="planes")
             for k, i in enumerate(idx):
                 images[i], masks[i] = im[k], mk[k]
         cams = []
         for i, c in enumerate(infos):
-            if tuple(images[i].shape[1:]) != (c.height, c.width):
-                raise ValueError(f"Scene: {c.image_path}: size changed while loading")
+            c = c._replace(width=int(images[i].shape[2]), height=int(images[i].shape[1]))  # (`resolution` leaves the FoVs alone)
             cam = S.TorchCamera(make_camera(c), self.device)
             cam.original_image, cam.gt_alpha_mask = images[i], masks[i]
             cam.uid, cam.image_name = i, c.image_name

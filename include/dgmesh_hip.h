@@ -57,7 +57,8 @@ extern "C" {
  *      Later additions that leave every existing entry point and layout unchanged keep the number: dgm_mc_* (marching cubes),
  *      dgm_tri_* (mesh rasterizer), dgm_anchor_* (Gaussian-mesh anchoring), dgm_ninit_* (entering the mesh phase),
  *      dgm_image_metrics* (test-view metrics), dgm_vertex_normals / dgm_mesh_shade / dgm_point_splat* / dgm_compose_frame
- *      (rendering a checkpoint), dgm_emd_* (mesh evaluation), dgm_png_unfilter / dgm_image_ingest (reading a dataset). */
+ *      (rendering a checkpoint), dgm_emd_* (mesh evaluation), dgm_png_unfilter / dgm_image_ingest (reading a dataset),
+ *      dgm_image_composite_bytes / dgm_resample (resizing a dataset's images). */
 #define DGM_ABI_VERSION 5
 
 /* Allocator callback: must return a device pointer to at least `bytes` bytes (128-byte aligned),
@@ -630,6 +631,35 @@ int dgm_emd_approx(int b, int n, int m, const float* xyz1, const float* xyz2, fl
  *       mask are 4-byte aligned; `in` is 4-byte aligned for C = 4 and may start at any byte for C = 3. */
 int dgm_png_unfilter(int B, int W, int H, int channels, const unsigned char* filtered, unsigned char* out, void* stream);
 int dgm_image_ingest(int B, int H, int W, int C, const unsigned char* in, const float* bg3, float* image, float* mask, void* stream);
+
+/* ---- image resampling: Pillow's 8-bit Image.resize on the device (csrc/resample.hip, csrc/ingest.hip) -----------------------------
+ * Replaces image.resize(..., LANCZOS) of readCamerasFromTransforms (dgmesh/scene/dataset_readers.py:289) and the bicubic
+ * image.resize of PILtoTorch (dgmesh/utils/general_utils.py:23-29).  The arithmetic is Pillow's, in integers: every output byte is
+ * clamp((2^21 + sum_k pixel[min + k] coeff[k]) >> 22, 0, 255) with an int32 accumulator and an arithmetic shift; a horizontal
+ * pass, a byte intermediate, a vertical pass.  The host computes the fixed-point coefficients (resample.coefficients).
+ *   dgm_image_composite_bytes: dgm_image_ingest's q (above) as bytes: out (B, H, W, 4) = (q_R, q_G, q_B, a), a = 255 for C = 3.
+ *       Same limits as dgm_image_ingest; out is 4-byte aligned.
+ *   dgm_resample: in (B, H, W, C) uint8, C 1, 3 or 4 -> (B, oh, ow, C).  All sizes within [1, 2^20], 1 <= B <= 65535.
+ *       Horizontal pass (run when kx != NULL; then ow may differ from W, otherwise ow == W): kx (ksize_x, owp) int32 with
+ *       owp = ow rounded up to a multiple of 4 -- tap-major, so that neighbouring lanes read neighbouring words -- and
+ *       bounds_x (2, owp) int32: row 0 the first input column of every output column, row 1 its tap count.  Taps past the count and
+ *       the padding columns are zero.  kx and bounds_x are 16-byte aligned.
+ *       Vertical pass (run when ky != NULL; otherwise oh == H): ky (oh, ksize_y) int32, bounds_y (oh, 2) int32 = (first input row,
+ *       tap count) of every output row.  At least one pass must run.  Input indices read from the tables are clamped into the
+ *       image and counts to ksize, so no table content can make the kernels read outside `in`.
+ *       tmp: (B, H, ow, C) bytes, used (and required) only when both passes run.
+ *       flags: DGM_RESAMPLE_PREMULTIPLIED (C = 4 only): colour bytes are premultiplied by alpha as the first pass loads them,
+ *       c' = ((t >> 8) + t) >> 8 with t = c a + 128, and divided out as the last pass stores them: unchanged for a = 0 or 255,
+ *       otherwise min(255, 255 c' / a) in integers.  DGM_RESAMPLE_PLANES (C = 3 or 4): the last pass writes image (B, 3, oh, ow) =
+ *       (float) byte / 255.0f, correctly rounded, and mask (B, oh, ow, 1) = (float) ((double) a / 255.0) (1 for C = 3) instead of
+ *       out_bytes (B, oh, ow, C).  The unused one of out_bytes and (image, mask) may be NULL.  in, tmp and out_bytes are 4-byte
+ *       aligned for C = 4 and may start at any byte otherwise; image and mask are 4-byte aligned. */
+#define DGM_RESAMPLE_PREMULTIPLIED 1
+#define DGM_RESAMPLE_PLANES 2
+int dgm_image_composite_bytes(int B, int H, int W, int C, const unsigned char* in, const float* bg3, unsigned char* out, void* stream);
+int dgm_resample(int B, int H, int W, int C, const unsigned char* in, int oh, int ow, const int* kx, const int* bounds_x, int ksize_x,
+                 const int* ky, const int* bounds_y, int ksize_y, int flags, unsigned char* tmp, unsigned char* out_bytes, float* image,
+                 float* mask, void* stream);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,10 @@ type drawn from all five, held in memory:
   * `stage_ms`: a page-locked buffer allocated and the scanlines copied into it; `upload_ms`: that buffer to the device;
   * `unfilter_ms`, `ingest_ms`: HIP events around dgm_png_unfilter and dgm_image_ingest for all frames, median of `iters`;
   * `ingest_GBps`: 20 bytes per pixel (4 in, 16 out) over ingest_ms.
+  * `lanczos_ms`: the frames halved (size -> size // 2) by resample.resize, Lanczos through Pillow's premultiplied RGBA path (two
+    launches of csrc/resample.hip), HIP events, median of `iters`; `lanczos_GBps`: bytes read and written by the two passes
+    (in + 2 x intermediate + out) over it; `pillow_lanczos_ms`: Image.resize of the same frames on one host thread, wall clock,
+    when Pillow imports (null otherwise); the device result of every distinct frame is compared with Pillow's.  Informational.
 The decoded pixels are compared with the images the files were made from.  No GPU: the script fails; it never falls back."""
 import argparse
 import importlib
@@ -115,10 +119,29 @@ def main():
     ingest_ms, (image, mask) = timed(lambda: D.image_ingest(pixels, [1.0, 1.0, 1.0]), args.iters)
     for k in range(len(files)):
         assert np.array_equal(pixels[k].cpu().numpy(), pictures[k]), f"frame {k} decoded wrongly"
+    RS = pkg("resample")
+    half = (W // 2, H // 2)
+    RS.resize(pixels, half, "lanczos")  # (warm-up; the coefficient tables are computed and uploaded here)
+    lanczos_ms, small = timed(lambda: RS.resize(pixels, half, "lanczos"), args.iters)
+    lanczos_bytes = B * C * (W * H + 2 * half[0] * H + half[0] * half[1])
+    pillow_ms = None
+    try:
+        from PIL import Image
+    except ImportError:
+        Image = None
+    if Image is not None:
+        want = [np.asarray(Image.fromarray(p, "RGBA").resize(half, Image.Resampling.LANCZOS)) for p in pictures]
+        t0 = time.perf_counter()
+        for k in range(B):
+            Image.fromarray(pictures[k % len(pictures)], "RGBA").resize(half, Image.Resampling.LANCZOS)
+        pillow_ms = (time.perf_counter() - t0) * 1e3
+        for k in range(len(pictures)):
+            assert np.array_equal(small[k].cpu().numpy(), want[k]), f"frame {k} resized differently from Pillow"
     print(json.dumps({"frames": B, "size": [W, H], "channels": C, "file_MB": sum(len(f) for f in frames) / 1e6,
                       "inflate_ms": inflate_ms, "inflate_workers": min(P.MAX_WORKERS, B), "stage_ms": stage_ms, "upload_ms": upload_ms,
                       "unfilter_ms": unfilter_ms, "ingest_ms": ingest_ms, "ingest_GBps": B * W * H * 20 / (ingest_ms * 1e-3) / 1e9,
-                      "unfilter_GBps": B * W * H * C * 2 / (unfilter_ms * 1e-3) / 1e9}))
+                      "unfilter_GBps": B * W * H * C * 2 / (unfilter_ms * 1e-3) / 1e9, "lanczos_size": list(half), "lanczos_ms": lanczos_ms,
+                      "lanczos_GBps": lanczos_bytes / (lanczos_ms * 1e-3) / 1e9, "pillow_lanczos_ms": pillow_ms}))
 
 
 if __name__ == "__main__":
