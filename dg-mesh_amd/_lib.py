@@ -69,6 +69,8 @@ SYMBOLS = {
     "dgm_image_loss_backward": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "dgm_image_metrics_workspace_bytes": (_c.c_size_t, [_i, _i, _i, _i, _i]),
     "dgm_image_metrics": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
+    "dgm_lpips_workspace_bytes": (_c.c_size_t, [_i, _i, _i, _i]),
+    "dgm_lpips": (_i, [_i, _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_vp), _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "dgm_gaussian_apply_forward": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "dgm_gaussian_apply_backward": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "dgm_se3_exp_forward": (_i, [_i, _vp, _i, _vp, _vp]),

@@ -5,8 +5,9 @@
 pytorch_msssim is not vendored and not a dependency: the MS-SSIM here is this project's own statement of that package's defaults
 (11-tap sigma-1.5 window without padding, five levels with weights 0.0448, 0.2856, 0.3001, 0.2363, 0.1333, 2x2 average pooling whose
 odd sides are zero-padded on both ends, relu on each level's term, mean over channels); tests/_metrics_ref.py restates it in numpy.
-LPIPS needs network weights and is not computed; the Chamfer / EMD metrics of exported meshes against ground truth (the
-reference's mesh_evaluation.py) are in mesh_eval.py.
+LPIPS (the reference's LPIPS_A and LPIPS_V) is computed by the kernels of csrc/lpips.hip through lpips.LPIPS objects that the caller
+builds from weight files of their own: the project ships none, and without them testing() reports the three metrics above.  The
+Chamfer / EMD metrics of exported meshes against ground truth (the reference's mesh_evaluation.py) are in mesh_eval.py.
 
 The reference copies four images to the host and makes six host round trips per view.  Here one dgm_image_metrics call per view
 scores the Gaussian image and the mesh image against the target and writes a row of a device-side table that is read back once,
@@ -15,6 +16,7 @@ import ctypes
 import os
 import time
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -84,8 +86,8 @@ def _mesh_view(mesh, gaussians, deform_back, d_xyz, d_normal, cam, white_backgro
 
 @torch.no_grad()
 def testing(gaussians, deform, deform_back, cameras, *, pipe, background, mesh=None, deform_normal=None, is_6dof=False,
-            white_background=True, out_dir=None, save_meshes=False):
-    """testing() of R/train.py:559-761 without LPIPS and without the image / glb files.  Per camera: deform.step at the camera's
+            white_background=True, out_dir=None, save_meshes=False, lpips=None):
+    """testing() of R/train.py:559-761 without the image / glb files.  Per camera: deform.step at the camera's
     fid, scene.render clamped to [0, 1]; with `mesh` (a trainer.MeshPhase that has a DPSR module) also mesh.psr -> mesh.surface ->
     deform_back + mesh.appearance on the vertices -> mesh_raster.render_mesh (deform_normal: the network whose first output is added
     to the normals; None = mesh.deform_normal).  One image_metrics call per view scores both images against cam.original_image
@@ -96,8 +98,14 @@ def testing(gaussians, deform, deform_back, cameras, *, pipe, background, mesh=N
     -> {"views": (n_views, 2, 4) float64 numpy array, "columns": COLUMNS, "gaussian": {column: mean}, "mesh": {column: mean} or
     None, "time_per_view": seconds, "fps": views per second}; the time is the wall time of the whole loop with one synchronisation
     at its end, metrics included (the reference times the two renders of each view on the host clock without synchronising).
-    out_dir: writes test_results/test_result.txt, the reference's two lines without their LPIPS fields, and with save_meshes
-    test_results/dynamic_mesh/frame_{idx}.ply with vertex colours (ply_io.write_mesh_ply)."""
+    out_dir: writes test_results/test_result.txt, the reference's two lines (their LPIPS fields only with `lpips`), and with save_meshes
+    test_results/dynamic_mesh/frame_{idx}.ply with vertex colours (ply_io.write_mesh_ply).
+
+    lpips: None, or {"alex": lpips.LPIPS, "vgg": lpips.LPIPS} with either key optional.  Each network then scores both images of a
+    view against the target in one call (the target's features are computed once) into a second device-side table that the same
+    read-back brings over, and the result gains "lpips": {"views": (n_views, 2, n_nets) float64, "nets": the nets in the order
+    alex, vgg, "gaussian": {net: mean}, "mesh": {net: mean} or None}; the two lines of test_result.txt gain ` LPIPS_A x.xxxx` /
+    ` LPIPS_V x.xxxx` after MSSSIM (R/train.py:754-755) for the nets given.  "views" and "columns" are the same with and without."""
     from . import scene as S
     if mesh is not None and mesh.dpsr is None:
         raise RuntimeError("testing: mesh must be a MeshPhase with a DPSR module")
@@ -110,6 +118,13 @@ def testing(gaussians, deform, deform_back, cameras, *, pipe, background, mesh=N
         deform_normal = mesh.deform_normal
     dev = gaussians.get_xyz.device
     table = torch.full((len(cameras), 2, 4), float("nan"), dtype=torch.float64, device=dev)
+    from . import lpips as LP
+    unknown = sorted(set(lpips or {}) - set(LP.NETS))
+    if unknown:
+        raise ValueError(f"testing: unknown lpips net(s): {', '.join(unknown)}")
+    nets = tuple(n for n in LP.NETS if n in (lpips or {}))
+    # (view, net, image, the five tap terms and their sum): rows that dgm_lpips writes whole
+    lp_table = torch.full((len(cameras), len(nets), 2, 6), float("nan"), dtype=torch.float64, device=dev) if nets else None
     saving_path = None if out_dir is None else os.path.join(out_dir, "test_results")
     if saving_path is not None:
         os.makedirs(saving_path, exist_ok=True)
@@ -132,21 +147,30 @@ def testing(gaussians, deform, deform_back, cameras, *, pipe, background, mesh=N
         ms = min(gt.shape[1:]) >= MS_SSIM_MIN_SIDE
         images, gt = _checked(images, gt, ms)
         _metrics_into(images, gt, table[idx, :images.shape[0]], 1.0, 5 if ms else 1)
+        for j, net in enumerate(nets):
+            lpips[net]._into(*LP._checked(images, gt, net), lp_table[idx, j, :images.shape[0]])
         if save_meshes:
             from .ply_io import write_mesh_ply
             write_mesh_ply(os.path.join(saving_path, "dynamic_mesh", f"frame_{idx}.ply"), verts, faces, vertex_colors=vtx_color)
     torch.cuda.synchronize(dev)
     total = time.perf_counter() - t0
-    views = table.cpu().numpy()  # the one read-back
+    both = table.flatten() if lp_table is None else torch.cat((table.flatten(), lp_table.flatten()))
+    host = both.cpu().numpy()  # the one read-back
+    views = host[:table.numel()].reshape(table.shape)
     mean = lambda row: {k: float(views[:, row, i].mean()) for i, k in enumerate(COLUMNS)}
     res = {"views": views, "columns": COLUMNS, "gaussian": mean(0), "mesh": mean(1) if mesh is not None else None,
            "time_per_view": total / len(cameras), "fps": len(cameras) / total}
+    if nets:
+        lp_views = np.ascontiguousarray(host[table.numel():].reshape(lp_table.shape)[..., 5].transpose(0, 2, 1))  # (view, image, net)
+        lp_mean = lambda row: {net: float(lp_views[:, row, j].mean()) for j, net in enumerate(nets)}
+        res["lpips"] = {"views": lp_views, "nets": nets, "gaussian": lp_mean(0), "mesh": lp_mean(1) if mesh is not None else None}
+    lp_fields = lambda name: "".join(f" LPIPS_{net[0].upper()} {res['lpips'][name][net]:.4f}" for net in nets)
     if saving_path is not None:
         a = res["gaussian"]
-        log = f"Gaussian image PSNR {a['psnr']:.4f} SSIM {a['ssim']:.4f} MSSSIM {a['ms_ssim']:.4f} \n"
+        log = f"Gaussian image PSNR {a['psnr']:.4f} SSIM {a['ssim']:.4f} MSSSIM {a['ms_ssim']:.4f}{lp_fields('gaussian')} \n"
         if mesh is not None:
             m = res["mesh"]
-            log += f"Mesh image PSNR {m['psnr']:.4f} SSIM {m['ssim']:.4f} MSSSIM {m['ms_ssim']:.4f} "
+            log += f"Mesh image PSNR {m['psnr']:.4f} SSIM {m['ssim']:.4f} MSSSIM {m['ms_ssim']:.4f}{lp_fields('mesh')} "
         log += f"total_time {res['time_per_view']:.4f} fps {res['fps']:.4f} \n"
         with open(os.path.join(saving_path, "test_result.txt"), "w") as fh:
             fh.write(log)

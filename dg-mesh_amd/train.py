@@ -11,6 +11,9 @@ file over them; `--key value` command-line overrides over that.  An unknown key 
 of IGNORED_KEYS, which the reference defines and this project has no use for, are dropped with one log line.  The merged dict is
 written to model_path/cfg_args.txt.
 
+LPIPS of the test views (--lpips_alex FILE, --lpips_vgg FILE): weight files in any layout lpips.py reads; the project ships none.
+With either, testing() also reports LPIPS_A / LPIPS_V; without, the run is what it was.
+
 Resuming (--start_checkpoint DIR): the Gaussians and every network of the latest iteration found in DIR are loaded and the loop
 continues with the iteration after it, so every schedule that is a function of the iteration number picks up where it was.
 Optimiser state is not saved, as in the reference, and the order in which frames are drawn starts over (Trainer.step_count counts
@@ -44,7 +47,7 @@ class ModelParams:
 
 # the driver's own switches (R/train.py:858-886 argparse flags)
 DRIVER_DEFAULTS = {"config": None, "start_checkpoint": None, "log_every": 1000, "save_iterations": None, "checkpoint_iterations": None,
-                   "seed": 0, "quiet": False}
+                   "seed": 0, "quiet": False, "lpips_alex": None, "lpips_vgg": None}
 # defined by the reference's parameter groups or command line, unused here
 # (gaussian_center: only real captures -- iPhone, NeuralActor -- place the DPSR cube by it; their readers are not built)
 IGNORED_KEYS = ("gaussian_center", "expname", "images", "data_device", "data_mask", "load2gpu_on_the_fly", "nerfies_ratio", "save_wis3d",
@@ -98,7 +101,7 @@ def load_yaml(path):
     return data
 
 
-PATH_KEYS = ("config", "start_checkpoint")                    # None by default, strings when given
+PATH_KEYS = ("config", "start_checkpoint", "lpips_alex", "lpips_vgg")  # None by default, strings when given
 LIST_KEYS = ("save_iterations", "checkpoint_iterations")      # None by default, lists of iterations when given
 
 
@@ -311,9 +314,13 @@ def training(cfg, *, gaussians=None, networks=None, log=print):
     if tests:
         from .evaluate import testing
         in_mesh = mesh is not None and iterations >= op.dpsr_iter
+        from .lpips import LPIPS
+        lpips = {net: LPIPS(net, cfg["lpips_" + net], dev) for net in ("alex", "vgg") if cfg["lpips_" + net]}
         test = testing(gaussians, deform, deform_back, tests, pipe=pp, background=background, mesh=mesh if in_mesh else None,
-                       is_6dof=lp.is_6dof, white_background=lp.white_background, out_dir=lp.model_path)
-        log(f"[TEST] {len(tests)} views: " + " ".join(f"{k} {v:.4f}" for k, v in test["gaussian"].items()))
+                       is_6dof=lp.is_6dof, white_background=lp.white_background, out_dir=lp.model_path,
+                       lpips=lpips or None)
+        log(f"[TEST] {len(tests)} views: " + " ".join(f"{k} {v:.4f}" for k, v in test["gaussian"].items())
+            + "".join(f" lpips_{net} {v:.4f}" for net, v in (test["lpips"]["gaussian"] if lpips else {}).items()))
     return {"log": history, "trainer": tr, "scene": scene, "gaussians": gaussians, "networks": nets, "mesh": mesh, "first_iter": first_iter,
             "saved": saved, "test": test}
 

@@ -58,7 +58,7 @@ extern "C" {
  *      dgm_tri_* (mesh rasterizer), dgm_anchor_* (Gaussian-mesh anchoring), dgm_ninit_* (entering the mesh phase),
  *      dgm_image_metrics* (test-view metrics), dgm_vertex_normals / dgm_mesh_shade / dgm_point_splat* / dgm_compose_frame
  *      (rendering a checkpoint), dgm_emd_* (mesh evaluation), dgm_png_unfilter / dgm_image_ingest (reading a dataset),
- *      dgm_image_composite_bytes / dgm_resample (resizing a dataset's images). */
+ *      dgm_image_composite_bytes / dgm_resample (resizing a dataset's images), dgm_lpips* (LPIPS of the test views). */
 #define DGM_ABI_VERSION 5
 
 /* Allocator callback: must return a device pointer to at least `bytes` bytes (128-byte aligned),
@@ -337,6 +337,27 @@ int dgm_image_loss_backward(const float* image, const float* gt, int channels, i
 size_t dgm_image_metrics_workspace_bytes(int B, int C, int H, int W, int levels);
 int dgm_image_metrics(const float* images, const float* gt, int B, int C, int H, int W, float data_range, int levels, char* workspace,
                       double* out, void* stream);
+
+/* LPIPS 0.1 of B images against ONE target (csrc/lpips.hip): images (B, 3, H, W) and gt (3, H, W), fp32 in [0, 1], row-major.
+ * net: 0 = alex, 1 = vgg.  Both inputs become ((2x - 1) - shift_c) / scale_c, shift = (-0.030, -0.088, -0.188), scale = (0.458,
+ * 0.448, 0.450), and run through the feature stack, every convolution followed by bias and ReLU:
+ *   alex: conv 3->64 k11 s4 p2 (tap), maxpool 3/2, conv 64->192 k5 p2 (tap), maxpool 3/2, conv 192->384 k3 p1 (tap),
+ *         conv 384->256 k3 p1 (tap), conv 256->256 k3 p1 (tap); min(H, W) >= 31.
+ *   vgg : all k3 p1: 64, 64 (tap), maxpool 2/2, 128, 128 (tap), maxpool, 256, 256, 256 (tap), maxpool, 512, 512, 512 (tap),
+ *         maxpool, 512, 512, 512 (tap); min(H, W) >= 16.
+ * Max-pools have stride 2, no padding and floor output size.  Tap k of an image (features a) and of the target (features b), both
+ * (h, w, C), gives mean over the h w pixels of sum_c lin_k[c] (a_c / (|a|_2 + 1e-10) - b_c / (|b|_2 + 1e-10))^2, norms over channels.
+ * out: (B, 6) float64 = the five tap terms and their sum.  The target's features are computed once per call.
+ * conv_w[i]: the i-th convolution's weight, packed (Kp, C_out) with row (ky kw + kx) C_in + c = weight[:, c, ky, kx] and
+ * Kp = kh kw C_in rounded up to a multiple of 16, the rows past kh kw C_in zero; conv_b[i]: (C_out); lin[k]: (C_k).  conv_w, conv_b
+ * and lin are HOST arrays (5 / 13 convolutions, 5 taps) of DEVICE pointers to fp32.
+ * Convolutions are fp32 (a k-ordered fma chain per output element), the tap terms fp64 over a fixed partition in a fixed order
+ * (no atomics): the results are bit-reproducible and row b does not depend on B.
+ * workspace: dgm_lpips_workspace_bytes(...) bytes, caller-owned, no initial state; 0 for unsupported arguments, which dgm_lpips
+ * refuses before any device work. */
+size_t dgm_lpips_workspace_bytes(int net, int B, int H, int W);
+int dgm_lpips(int net, const float* const* conv_w, const float* const* conv_b, const float* const* lin, const float* images,
+              const float* gt, int B, int H, int W, char* workspace, double* out, void* stream);
 
 /* ---- per-Gaussian glue of the train step ------------------------------------------------------------------ */
 
