@@ -130,8 +130,11 @@ SYMBOLS = {
     "dgm_emd_approx": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dgm_png_unfilter": (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
     "dgm_image_ingest": (_i, [_i, _i, _i, _i, _vp, _c.POINTER(_f), _vp, _vp, _vp]),
+    "dgm_png_expand": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "dgm_image_ingest_masked": (_i, [_i, _i, _i, _i, _vp, _i, _vp, _c.POINTER(_f), _i, _vp, _vp, _vp, _vp]),
     "dgm_image_composite_bytes": (_i, [_i, _i, _i, _i, _vp, _c.POINTER(_f), _vp, _vp]),
     "dgm_resample": (_i, [_i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_resample_nearest": (_i, [_i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "dgm_mlp_set_gemm": (_i, [_i]),
     "dgm_timenet_forward": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "dgm_timenet_backward": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

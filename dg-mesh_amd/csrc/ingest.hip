@@ -13,6 +13,11 @@
 //                    walked in bands by the same workgroup: row 0 of a later band reads `up` from the finished row above in `out`.
 //   ingest kernel  : four pixels per thread (16 bytes in, 4 x 16 bytes out), fp64 arithmetic in the reference's order.
 //   composite kernel: the same bytes before the division, as (R, G, B, file alpha) words: the input of a `resolution` resize.
+//   expand kernel  : the packed rows of a 1-, 2-, 4- or 8-bit grey or palette image (unfiltered as bytes: W' = row bytes, CH = 1)
+//                    as one byte per pixel, most significant bits first, times Pillow's grey scale (255, 85, 17, 1) or 1 for indices.
+//   masked ingest  : the real captures' compositing (readNerfiesCameras, readiPhoneCameras, readNeuralActorCameras,
+//                    R/scene/dataset_readers.py:545-865): the frame where channel 0 of the mask is set, the background elsewhere;
+//                    planes (byte / 255, mask > 0) or (R, G, B, 255 (mask > 0)) words for a `resolution` resize.
 //
 // Built with -ffp-contract=off and correctly rounded fp32 division: (n_c n_a + bg (1 - n_a)) 255 truncates to a different byte than
 // any contracted or integer form for some (colour, alpha) pairs.
@@ -40,6 +45,7 @@ __device__ __forceinline__ unsigned paeth(unsigned a, unsigned b, unsigned c) {
 template <int CH, bool ALIGNED>
 __device__ __forceinline__ unsigned load_pixel(const unsigned char* p) {
     if (CH == 4) return ALIGNED ? *(const unsigned*)p : *(const dgm_u32b*)p;
+    if (CH == 1) return (unsigned)p[0];
     return (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16);
 }
 
@@ -89,6 +95,8 @@ __global__ __launch_bounds__(UF_ROWS) void png_unfilter_kernel(int W, int H, con
                 unsigned char* d = drow + (size_t)x * CH;
                 if (CH == 4) {
                     *(unsigned*)d = o;
+                } else if (CH == 1) {
+                    d[0] = (unsigned char)o;
                 } else {
                     d[0] = (unsigned char)(o & 255u);
                     d[1] = (unsigned char)((o >> 8) & 255u);
@@ -207,6 +215,78 @@ __global__ __launch_bounds__(256) void image_composite_kernel(long long HW, cons
     }
 }
 
+// one byte per pixel from rows of ceil(W depth / 8) packed bytes; the bits past a row's last pixel are never looked at
+__global__ __launch_bounds__(256) void png_expand_kernel(long long HW, int W, int depth, unsigned scale, const unsigned char* __restrict__ in,
+                                                         unsigned char* __restrict__ out) {
+    const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (n >= HW) return;
+    const size_t b = blockIdx.y;
+    const long long y = n / W;
+    const long long bit = (n - y * W) * depth;
+    const size_t row_bytes = ((size_t)W * depth + 7) >> 3;
+    const size_t H = (size_t)(HW / W);
+    const unsigned byte = in[(b * H + (size_t)y) * row_bytes + (size_t)(bit >> 3)];
+    const unsigned v = (byte >> (8 - depth - (int)(bit & 7))) & ((1u << depth) - 1u);
+    out[b * (size_t)HW + (size_t)n] = (unsigned char)(v * scale);
+}
+
+// the frame where the mask's channel 0 is set, the background's byte elsewhere.  BYTES: (R, G, B, 255 (m > 0)) words; otherwise the
+// planes image = byte / 255 (the division of image_ingest_kernel) and alpha = m > 0
+template <int C, bool BYTES>
+__global__ __launch_bounds__(256) void image_ingest_masked_kernel(long long HW, const unsigned char* __restrict__ in, int Cm,
+                                                                  const unsigned char* __restrict__ mask, double bg0, double bg1, double bg2,
+                                                                  float* __restrict__ image, float* __restrict__ alpha,
+                                                                  unsigned char* __restrict__ bytes_out) {
+    const long long n0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (n0 >= HW) return;
+    const size_t b = blockIdx.y;
+    const size_t at = b * (size_t)HW + (size_t)n0;
+    const unsigned char* src = in + at * C;
+    const unsigned char* msrc = mask + at * (size_t)Cm;
+    const unsigned bgb[3] = {composite_byte(0u, 0.0, bg0), composite_byte(0u, 0.0, bg1), composite_byte(0u, 0.0, bg2)};
+    const unsigned bgw = bgb[0] | (bgb[1] << 8) | (bgb[2] << 16);
+    if (n0 + 4 <= HW) {
+        unsigned px[4];
+        load4_rgba<C>(src, px);
+        bool on[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            on[k] = msrc[(size_t)k * Cm] != 0;
+            px[k] = on[k] ? ((px[k] & 0xffffffu) | 0xff000000u) : bgw;
+        }
+        if (BYTES) {
+            dgm_u4u o;
+#pragma unroll
+            for (int k = 0; k < 4; k++) o[k] = px[k];
+            *(dgm_u4u*)((unsigned*)bytes_out + at) = o;
+        } else {
+            dgm_f4u m;
+#pragma unroll
+            for (int k = 0; k < 4; k++) m[k] = on[k] ? 1.0f : 0.0f;
+            *(dgm_f4u*)(alpha + at) = m;
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                dgm_f4u o;
+#pragma unroll
+                for (int k = 0; k < 4; k++) o[k] = (float)((px[k] >> (8 * c)) & 255u) / 255.0f;
+                *(dgm_f4u*)(image + b * 3 * (size_t)HW + (size_t)c * HW + (size_t)n0) = o;
+            }
+        }
+    } else {  // the last one to three pixels of an image whose pixel count is no multiple of four
+        for (long long k = 0; n0 + k < HW; k++) {
+            const unsigned char* p = src + k * C;
+            const bool on = msrc[(size_t)k * Cm] != 0;
+            const unsigned w = on ? ((unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16) | 0xff000000u) : bgw;
+            if (BYTES) {
+                ((unsigned*)bytes_out)[at + k] = w;
+            } else {
+                alpha[at + k] = on ? 1.0f : 0.0f;
+                for (int c = 0; c < 3; c++) image[b * 3 * (size_t)HW + (size_t)c * HW + (size_t)(n0 + k)] = (float)((w >> (8 * c)) & 255u) / 255.0f;
+            }
+        }
+    }
+}
+
 static int launch_status(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -225,14 +305,17 @@ using namespace dgm;
 extern "C" {
 
 int dgm_png_unfilter(int B, int W, int H, int channels, const unsigned char* filtered, unsigned char* out, void* stream) {
-    if (B < 1 || W < 1 || H < 1 || W > (1 << 24) || H > (1 << 24) || (channels != 3 && channels != 4) || !filtered || !out ||
-        ((uintptr_t)out & 3)) {
-        set_last_error("png_unfilter: bad argument (B >= 1, 1 <= W, H <= 2^24, channels 3 or 4, no null pointer, out 4-byte aligned)");
+    if (B < 1 || W < 1 || H < 1 || W > (1 << 24) || H > (1 << 24) || (channels != 1 && channels != 3 && channels != 4) || !filtered || !out ||
+        (channels != 1 && ((uintptr_t)out & 3))) {
+        set_last_error("png_unfilter: bad argument (B >= 1, 1 <= W, H <= 2^24, channels 1, 3 or 4, no null pointer, out 4-byte aligned "
+                       "unless channels is 1)");
         return 1;
     }
     hipStream_t st = (hipStream_t)stream;
     if (channels == 4)
         hipLaunchKernelGGL(png_unfilter_kernel<4>, dim3(B), dim3(UF_ROWS), 0, st, W, H, filtered, out);
+    else if (channels == 1)
+        hipLaunchKernelGGL(png_unfilter_kernel<1>, dim3(B), dim3(UF_ROWS), 0, st, W, H, filtered, out);
     else
         hipLaunchKernelGGL(png_unfilter_kernel<3>, dim3(B), dim3(UF_ROWS), 0, st, W, H, filtered, out);
     return launch_status("png_unfilter");
@@ -280,6 +363,55 @@ int dgm_image_composite_bytes(int B, int H, int W, int C, const unsigned char* i
     else
         hipLaunchKernelGGL(image_composite_kernel<3>, grid, dim3(256), 0, st, HW, in, (double)bg3[0], (double)bg3[1], (double)bg3[2], out);
     return launch_status("image_composite_bytes");
+}
+
+int dgm_png_expand(int B, int W, int H, int depth, int scale, const unsigned char* packed, unsigned char* out, void* stream) {
+    if (B < 1 || B > 65535 || W < 1 || H < 1 || W > (1 << 24) || H > (1 << 24) || (depth != 1 && depth != 2 && depth != 4 && depth != 8) ||
+        scale < 1 || (long long)scale * ((1 << depth) - 1) > 255 || !packed || !out) {
+        set_last_error("png_expand: bad argument (1 <= B <= 65535, 1 <= W, H <= 2^24, depth 1, 2, 4 or 8, scale >= 1 with "
+                       "scale (2^depth - 1) <= 255, no null pointer)");
+        return 1;
+    }
+    const long long HW = (long long)H * W;
+    const long long blocks = (HW + 255) / 256;
+    if (blocks > 0x7fffffffLL) {
+        set_last_error("png_expand: image too large");
+        return 1;
+    }
+    hipLaunchKernelGGL(png_expand_kernel, dim3((unsigned)blocks, (unsigned)B), dim3(256), 0, (hipStream_t)stream, HW, W, depth, (unsigned)scale,
+                       packed, out);
+    return launch_status("png_expand");
+}
+
+int dgm_image_ingest_masked(int B, int H, int W, int C, const unsigned char* in, int Cm, const unsigned char* mask, const float* bg3, int flags,
+                            float* image, float* alpha, unsigned char* bytes_out, void* stream) {
+    const bool bytes = (flags & DGM_INGEST_BYTES) != 0;
+    if (B < 1 || B > 65535 || W < 1 || H < 1 || W > (1 << 24) || H > (1 << 24) || (C != 3 && C != 4) || (Cm != 1 && Cm != 3 && Cm != 4) ||
+        (flags & ~DGM_INGEST_BYTES) || !in || !mask || !bg3 || (C == 4 && ((uintptr_t)in & 3)) ||
+        (bytes ? (!bytes_out || ((uintptr_t)bytes_out & 3)) : (!image || !alpha || ((uintptr_t)image & 3) || ((uintptr_t)alpha & 3)))) {
+        set_last_error("image_ingest_masked: bad argument (1 <= B <= 65535, 1 <= W, H <= 2^24, C 3 or 4, Cm 1, 3 or 4, flags 0 or "
+                       "DGM_INGEST_BYTES, no null pointer among in, mask, bg3 and the selected output, outputs 4-byte aligned, in 4-byte "
+                       "aligned when C is 4)");
+        return 1;
+    }
+    const long long HW = (long long)H * W;
+    const long long blocks = ((HW + 3) / 4 + 255) / 256;
+    if (blocks > 0x7fffffffLL) {
+        set_last_error("image_ingest_masked: image too large");
+        return 1;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)blocks, (unsigned)B);
+    const double b0 = (double)bg3[0], b1 = (double)bg3[1], b2 = (double)bg3[2];
+    if (C == 4 && bytes)
+        hipLaunchKernelGGL((image_ingest_masked_kernel<4, true>), grid, dim3(256), 0, st, HW, in, Cm, mask, b0, b1, b2, image, alpha, bytes_out);
+    else if (C == 4)
+        hipLaunchKernelGGL((image_ingest_masked_kernel<4, false>), grid, dim3(256), 0, st, HW, in, Cm, mask, b0, b1, b2, image, alpha, bytes_out);
+    else if (bytes)
+        hipLaunchKernelGGL((image_ingest_masked_kernel<3, true>), grid, dim3(256), 0, st, HW, in, Cm, mask, b0, b1, b2, image, alpha, bytes_out);
+    else
+        hipLaunchKernelGGL((image_ingest_masked_kernel<3, false>), grid, dim3(256), 0, st, HW, in, Cm, mask, b0, b1, b2, image, alpha, bytes_out);
+    return launch_status("image_ingest_masked");
 }
 
 }  // extern "C"

@@ -266,6 +266,24 @@ static void launch_passes(int B, int H, int W, const unsigned char* in, int oh, 
                            ksize_y, kx ? (const unsigned char*)tmp : in, ky, bounds_y, premultiplied && !kx, premultiplied, out);
 }
 
+// Pillow's NEAREST (what Image.resize does to modes P and 1 whatever filter is asked for): out[y][x] = in[ys[y]][xs[x]], the index
+// tables computed on the host (resample.nearest_indices); indices are clamped into the image
+template <int C>
+__global__ __launch_bounds__(64 * RS_ROWS) void resample_nearest_kernel(int H, int W, int oh, int ow, const unsigned char* __restrict__ in,
+                                                                       const int* __restrict__ xs, const int* __restrict__ ys,
+                                                                       unsigned char* __restrict__ out) {
+    const int y = (int)blockIdx.x * RS_ROWS + (int)threadIdx.y, x = (int)blockIdx.y * 64 + (int)threadIdx.x;
+    if (y >= oh || x >= ow) return;
+    const size_t b = blockIdx.z;
+    int sx = xs[x], sy = ys[y];
+    sx = sx < 0 ? 0 : (sx >= W ? W - 1 : sx);
+    sy = sy < 0 ? 0 : (sy >= H ? H - 1 : sy);
+    const unsigned char* s = in + ((b * H + (size_t)sy) * W + (size_t)sx) * C;
+    unsigned char* d = out + ((b * oh + (size_t)y) * ow + (size_t)x) * C;
+#pragma unroll
+    for (int c = 0; c < C; c++) d[c] = s[c];
+}
+
 }  // namespace dgm
 
 using namespace dgm;
@@ -322,6 +340,33 @@ extern "C" int dgm_resample(int B, int H, int W, int C, const unsigned char* in,
     if (e != hipSuccess) {
         static thread_local char m[256];
         snprintf(m, sizeof m, "resample: %s", hipGetErrorString(e));
+        set_last_error(m);
+        return 1;
+    }
+    return 0;
+}
+
+extern "C" int dgm_resample_nearest(int B, int H, int W, int C, const unsigned char* in, int oh, int ow, const int* xs, const int* ys,
+                                    unsigned char* out, void* stream) {
+    const int LIM = 1 << 20;
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || oh < 1 || ow < 1 || H > LIM || W > LIM || oh > LIM || ow > LIM || (C != 1 && C != 3 && C != 4) ||
+        !in || !xs || !ys || !out || ((uintptr_t)xs & 3) || ((uintptr_t)ys & 3)) {
+        set_last_error("resample_nearest: bad argument (1 <= B <= 65535, every size within [1, 2^20], C 1, 3 or 4, no null pointer, xs and ys "
+                       "4-byte aligned)");
+        return 1;
+    }
+    const dim3 grid((unsigned)((oh + RS_ROWS - 1) / RS_ROWS), (unsigned)((ow + 63) / 64), (unsigned)B), block(64, RS_ROWS);
+    hipStream_t st = (hipStream_t)stream;
+    if (C == 4)
+        hipLaunchKernelGGL(resample_nearest_kernel<4>, grid, block, 0, st, H, W, oh, ow, in, xs, ys, out);
+    else if (C == 3)
+        hipLaunchKernelGGL(resample_nearest_kernel<3>, grid, block, 0, st, H, W, oh, ow, in, xs, ys, out);
+    else
+        hipLaunchKernelGGL(resample_nearest_kernel<1>, grid, block, 0, st, H, W, oh, ow, in, xs, ys, out);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        static thread_local char m[256];
+        snprintf(m, sizeof m, "resample_nearest: %s", hipGetErrorString(e));
         set_last_error(m);
         return 1;
     }

@@ -17,7 +17,9 @@ Deviation from the reference: it swaps the two field-of-view names (FovY = fovx;
 harmless for square images and wrong otherwise.  Here FoVx is the file's camera_angle_x and FoVy follows from the aspect ratio.
 Under `resolution` the reference resizes the image and leaves the alpha mask at its old size, so its mask loss cannot run; here the
 alpha plane is resampled with the same bicubic filter as a fourth, non-premultiplied channel and the mask always has the image's size.
-Not built: Nerfies, iPhone and NeuralActor scenes have other readers in the reference; they raise by name here.
+Nerfies, iPhone and NeuralActor scenes have other readers in the reference; theirs are in captures.py, which Scene asks first
+(READERS here keeps a stub per name that raises).  Their cameras carry an intrinsic matrix K and a mask_path: Scene._load decodes
+the masks beside the frames (png_io.decode_mask_groups) and composites with image_ingest_masked.
 read_blender_scene itself still reads at file size only (downsample=1.0); Scene applies `downsample`."""
 import ctypes
 import json
@@ -51,6 +53,8 @@ class CameraInfo(NamedTuple):
     width: int
     height: int
     fid: float
+    K: np.ndarray = None   # (3, 3) float64 intrinsics of a real capture, for width x height; None: the FoVs describe the camera
+    mask_path: str = None  # the segmentation mask of a real capture's frame
 
 
 class PointCloud(NamedTuple):
@@ -82,7 +86,10 @@ def world_to_view(R, T):
 def make_camera(info):
     """synthetic.Camera of a CameraInfo, built as R/scene/cameras.py:54-71 builds its matrices."""
     wvt = np.ascontiguousarray(world_to_view(info.R, info.T).T)
-    P = synthetic.projection_matrix(ZNEAR, ZFAR, info.FoVx, info.FoVy)
+    if info.K is not None:  # (R/scene/cameras.py:64-67: getProjectionMatrix_from_K when the camera has intrinsics)
+        P = synthetic.projection_matrix_from_K(ZNEAR, ZFAR, np.asarray(info.K, np.float64), info.width, info.height)
+    else:
+        P = synthetic.projection_matrix(ZNEAR, ZFAR, info.FoVx, info.FoVy)
     full = np.ascontiguousarray((wvt @ P.T).astype(np.float32))
     center = np.linalg.inv(wvt.astype(np.float64))[3, :3].astype(np.float32)
     return synthetic.Camera(info.width, info.height, info.FoVx, info.FoVy, wvt, full, center, float(info.fid))
@@ -231,6 +238,37 @@ def image_composite_bytes(pixels, background):
     return out
 
 
+def image_ingest_masked(pixels, mask, background, out="planes"):
+    """dgm_image_ingest_masked: pixels (B, H, W, 3 or 4) uint8 and mask (B, H, W, 1, 3 or 4) uint8 on the device; m = mask[..., 0] > 0.
+    out="planes" -> original_image (B, 3, H, W) fp32 = (m ? byte : 255 background) / 255, gt_alpha_mask (B, H, W, 1) fp32 = m.
+    out="bytes"  -> (B, H, W, 4) uint8 = (R, G, B, 255 m): what a `resolution` resize takes."""
+    import torch
+
+    from . import _lib
+    ok = lambda t, cs: torch.is_tensor(t) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 4 and t.shape[3] in cs
+    if not (ok(pixels, (3, 4)) and ok(mask, (1, 3, 4))):
+        raise RuntimeError("image_ingest_masked needs (B, H, W, 3 or 4) and (B, H, W, 1, 3 or 4) uint8 CUDA/HIP tensors (dg-mesh_amd has no "
+                           "CPU path for its kernels)")
+    if out not in ("planes", "bytes"):
+        raise ValueError(f"image_ingest_masked: out must be 'planes' or 'bytes', got {out!r}")
+    if pixels.shape[:3] != mask.shape[:3] or pixels.device != mask.device:
+        raise ValueError(f"image_ingest_masked: pixels {tuple(pixels.shape)} and mask {tuple(mask.shape)} differ in batch, size or device")
+    pixels, mask = pixels.contiguous(), mask.contiguous()
+    B, H, W, C = pixels.shape
+    image = alpha = res = None
+    if out == "planes":
+        image = torch.empty((B, 3, H, W), dtype=torch.float32, device=pixels.device)
+        alpha = torch.empty((B, H, W, 1), dtype=torch.float32, device=pixels.device)
+    else:
+        res = torch.empty((B, H, W, 4), dtype=torch.uint8, device=pixels.device)
+    bg = (ctypes.c_float * 3)(*[float(v) for v in background])
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)
+    with _lib.device_guard(pixels.device):
+        _lib.check(_lib.lib().dgm_image_ingest_masked(B, H, W, C, ptr(pixels), int(mask.shape[3]), ptr(mask), bg, 1 if res is not None else 0,
+                                                      ptr(image), ptr(alpha), ptr(res), _lib.stream_ptr()))
+    return (image, alpha) if res is None else res
+
+
 def downsampled(info, downsample):
     """The CameraInfo after readCamerasFromTransforms' image.resize((int(W / downsample), int(H / downsample))): width, height, and
     FoVy recomputed from the resized size; FoVx stays the file's camera_angle_x."""
@@ -276,12 +314,19 @@ class Scene:
                 load_iteration = max(int(f.split("_")[-1]) for f in os.listdir(os.path.join(self.model_path, "point_cloud")))
             self.loaded_iter = load_iteration
         os.makedirs(self.model_path, exist_ok=True)
-        info = READERS[scene_type(args)](args.source_path, args.white_background, args.eval, downsample=1.0,
-                                         model_path=self.model_path, seed=seed)
+        from . import captures
+        kind = scene_type(args)
         d = float(getattr(args, "downsample", 1.0))
         if not d > 0:
             raise ValueError(f"Scene: downsample must be positive, got {d}")
-        if d != 1.0:  # (the reader saw the files' sizes; from here on the cameras carry the downsampled ones)
+        if kind in captures.READERS:
+            # the capture readers size their cameras themselves (K follows the image); only Nerfies scenes take `downsample`
+            more = {"downsample": d, "nerfies_ratio": float(getattr(args, "nerfies_ratio", 0.5))} if kind == "Nerfies" else {}
+            info = captures.READERS[kind](args.source_path, args.white_background, args.eval, model_path=self.model_path, seed=seed, **more)
+            d = d if kind == "Nerfies" else 1.0
+        else:
+            info = READERS[kind](args.source_path, args.white_background, args.eval, downsample=1.0, model_path=self.model_path, seed=seed)
+        if d != 1.0 and kind not in captures.READERS:  # (the reader saw the files' sizes; from here on the cameras carry the downsampled ones)
             info = info._replace(train_cameras=[downsampled(c, d) for c in info.train_cameras],
                                  test_cameras=[downsampled(c, d) for c in info.test_cameras])
         self.downsample, self.resolution = d, getattr(args, "resolution", -1)
@@ -317,6 +362,8 @@ class Scene:
         if not infos:
             return []
         images, masks = [None] * len(infos), [None] * len(infos)
+        capture = infos[0].mask_path is not None
+        seg, per = self._load_masks(infos) if capture else (None, None)
         for idx, pixels in png_io.decode_png_groups([c.image_path for c in infos], self.device):
             w, h = resample.target_size_downsample(pixels.shape[2], pixels.shape[1], self.downsample)
             if any((infos[i].width, infos[i].height) != (w, h) for i in idx):  # (the sizes the reader took from the headers)
@@ -326,7 +373,16 @@ class Scene:
             final = resample.target_size_resolution(w, h, self.resolution)
             if min(final) < 1:
                 raise ValueError(f"Scene: resolution={self.resolution} leaves no pixels of a {w} x {h} image")
-            if final == (w, h):
+            if capture:
+                import torch
+                whole = [b for j, b in seg if j == idx]  # one mask batch for exactly these frames: taken as it is
+                mk = whole[0] if whole else torch.stack([per[i][:, :, :1] for i in idx])
+                if final == (w, h):
+                    im, mk = image_ingest_masked(pixels, mk, background)
+                else:
+                    im, mk = resample.resize(image_ingest_masked(pixels, mk, background, out="bytes"), final, "bicubic", premultiplied=False,
+                                             out="planes")
+            elif final == (w, h):
                 im, mk = image_ingest(pixels, background)
             else:
                 im, mk = resample.resize(image_composite_bytes(pixels, background), final, "bicubic", premultiplied=False, out="planes")
@@ -334,12 +390,35 @@ class Scene:
                 images[i], masks[i] = im[k], mk[k]
         cams = []
         for i, c in enumerate(infos):
-            c = c._replace(width=int(images[i].shape[2]), height=int(images[i].shape[1]))  # (`resolution` leaves the FoVs alone)
+            fw, fh = int(images[i].shape[2]), int(images[i].shape[1])
+            if c.K is not None and (fw, fh) != (c.width, c.height):  # (the intrinsics follow the image, so the frustum stays)
+                c = c._replace(K=np.diag([fw / c.width, fh / c.height, 1.0]) @ np.asarray(c.K, np.float64))
+            c = c._replace(width=fw, height=fh)  # (`resolution` leaves the FoVs alone)
             cam = S.TorchCamera(make_camera(c), self.device)
             cam.original_image, cam.gt_alpha_mask = images[i], masks[i]
             cam.uid, cam.image_name = i, c.image_name
             cams.append(cam)
         return cams
+
+    def _load_masks(self, infos):
+        """([(indices, (n, h, w, C) uint8 batch)], {camera index: its (h, w, C) view}) of the cameras' masks at the cameras' size:
+        decoded, and under `downsample` resized as Pillow resizes them -- NEAREST for palette and bilevel files, Lanczos for grey and
+        colour ones."""
+        for c in infos:
+            if c.mask_path is None or not os.path.exists(c.mask_path):
+                raise ValueError(f"Scene: {c.image_path}: its mask {c.mask_path} is missing")
+        out = []
+        for idx, batch, kind in png_io.decode_mask_groups([c.mask_path for c in infos], self.device):
+            W, H = int(batch.shape[2]), int(batch.shape[1])
+            for i in idx:  # (the files' own sizes: two different sizes can meet after `downsample`)
+                fw, fh = (int(v) for v in png_size(infos[i].image_path))
+                if (fw, fh) != (W, H):
+                    raise ValueError(f"Scene: the mask {infos[i].mask_path} is {W} x {H} but its frame {infos[i].image_path} is {fw} x {fh}")
+            w, h = resample.target_size_downsample(W, H, self.downsample)
+            if (w, h) != (W, H):
+                batch = resample.resize_nearest(batch, (w, h)) if kind == "index" else resample.resize(batch, (w, h), "lanczos")
+            out.append((idx, batch))
+        return out, {i: b[k] for idx, b in out for k, i in enumerate(idx)}
 
     def save(self, iteration):
         self.gaussians.save_ply(os.path.join(self.model_path, f"point_cloud/iteration_{iteration}", "point_cloud.ply"))

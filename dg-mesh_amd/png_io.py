@@ -3,7 +3,11 @@ library only (zlib + struct) -- imageio, PIL and cv2 are not dependencies.
 
 PNG reader for dataset.py: parse_png checks a file and inflates its IDAT stream on the host (zlib, at C speed); the byte-serial
 part of decoding -- undoing the per-row filters -- runs on the device (decode_pngs -> dgm_png_unfilter, csrc/ingest.hip).  8-bit
-RGB and RGBA without interlace, which is what the Blender / D-NeRF scenes ship; anything else is refused by name."""
+RGB and RGBA without interlace, which is what the Blender / D-NeRF scenes ship; anything else is refused by name.
+
+The segmentation masks of real captures (captures.py) are palette, grey and bilevel files, often of 1, 2 or 4 bits per pixel:
+parse_png_any reads those as well, decode_mask_groups unfilters their packed rows as bytes (the PNG filters of a sub-byte image work
+on whole bytes) and dgm_png_expand turns them into one byte per pixel, with Pillow's scaling of grey samples."""
 import ctypes
 import os
 import struct
@@ -35,10 +39,8 @@ def write_png(path, image, compress_level=6):
         fh.write(data)
 
 
-def parse_png(src):
-    """src: a path or the file's bytes -> (W, H, channels, filtered): `filtered` is the inflated IDAT stream, H rows of
-    1 + W * channels bytes, each led by its filter type (0..4, checked here).  ValueError, naming the file and the reason, for
-    anything but an intact 8-bit RGB / RGBA PNG without interlace."""
+def _read_chunks(src, who):
+    """-> (name, bad, IHDR fields, joined IDAT bytes, whether a PLTE chunk was seen) of an intact chunk sequence."""
     if isinstance(src, (bytes, bytearray, memoryview)):
         name, data = "<bytes>", bytes(src)
     else:
@@ -47,11 +49,11 @@ def parse_png(src):
             data = fh.read()
 
     def bad(why):
-        return ValueError(f"parse_png: {name}: {why}")
+        return ValueError(f"{who}: {name}: {why}")
 
     if data[:8] != SIGNATURE:
         raise bad("not a PNG file (bad signature)")
-    pos, header, idat, ended = 8, None, [], False
+    pos, header, idat, ended, palette = 8, None, [], False, False
     while pos < len(data):
         if pos + 8 > len(data):
             raise bad("truncated (chunk header cut short)")
@@ -68,6 +70,8 @@ def parse_png(src):
             if n != 13:
                 raise bad("IHDR is not 13 bytes")
             header = struct.unpack(">IIBBBBB", body)
+        elif tag == b"PLTE":
+            palette = True
         elif tag == b"IDAT":
             idat.append(body)
         elif tag == b"IEND":
@@ -75,6 +79,30 @@ def parse_png(src):
             break
     if header is None or not ended:
         raise bad("truncated (no IEND chunk)")
+    return name, bad, header, b"".join(idat), palette
+
+
+def _inflate_rows(bad, idat, H, row_bytes, what):
+    """The inflated IDAT stream, H rows of 1 + row_bytes bytes, with its length and filter types checked."""
+    try:
+        filtered = zlib.decompress(idat)
+    except zlib.error as e:
+        raise bad(f"truncated or corrupt IDAT stream ({e})") from None
+    stride = 1 + row_bytes
+    if len(filtered) != H * stride:
+        raise bad(f"the IDAT stream inflates to {len(filtered)} bytes, not H * (1 + {what}) = {H * stride}")
+    types = np.frombuffer(filtered, np.uint8)[::stride]
+    if types.max() > 4:
+        row = int(np.argmax(types > 4))
+        raise bad(f"bad filter type {int(types[row])} on row {row}")
+    return filtered
+
+
+def parse_png(src):
+    """src: a path or the file's bytes -> (W, H, channels, filtered): `filtered` is the inflated IDAT stream, H rows of
+    1 + W * channels bytes, each led by its filter type (0..4, checked here).  ValueError, naming the file and the reason, for
+    anything but an intact 8-bit RGB / RGBA PNG without interlace."""
+    name, bad, header, idat, _ = _read_chunks(src, "parse_png")
     W, H, depth, colour, compression, filter_method, interlace = header
     if W < 1 or H < 1:
         raise bad(f"empty image {W}x{H}")
@@ -87,22 +115,44 @@ def parse_png(src):
     if compression != 0 or filter_method != 0:
         raise bad("unknown compression or filter method")
     channels = 3 if colour == 2 else 4
-    try:
-        filtered = zlib.decompress(b"".join(idat))
-    except zlib.error as e:
-        raise bad(f"truncated or corrupt IDAT stream ({e})") from None
-    stride = 1 + W * channels
-    if len(filtered) != H * stride:
-        raise bad(f"the IDAT stream inflates to {len(filtered)} bytes, not H * (1 + W * channels) = {H * stride}")
-    types = np.frombuffer(filtered, np.uint8)[::stride]
-    if types.max() > 4:
-        row = int(np.argmax(types > 4))
-        raise bad(f"bad filter type {int(types[row])} on row {row}")
-    return W, H, channels, filtered
+    return W, H, channels, _inflate_rows(bad, idat, H, W * channels, "W * channels")
+
+
+_ANY_CHANNELS = {0: 1, 3: 1, 2: 3, 6: 4}
+
+
+def parse_png_any(src):
+    """parse_png for the files masks come in as well: -> (W, H, colour, depth, row_bytes, bpp, filtered).  Colour types 0 (grey)
+    and 3 (palette; a PLTE chunk must be there, its entries are not needed: a mask is tested against index 0) at bit depths 1, 2,
+    4 and 8; 2 (RGB) and 6 (RGBA) at depth 8.  row_bytes = ceil(W * channels * depth / 8), bpp = max(1, channels * depth / 8) =
+    the distance in bytes between a byte and its `left` neighbour under the PNG filters; `filtered`: H rows of 1 + row_bytes bytes.
+    ValueError by name for 16-bit samples, grey + alpha (type 4), interlace, a bad CRC or filter byte, a cut file."""
+    name, bad, header, idat, palette = _read_chunks(src, "parse_png_any")
+    W, H, depth, colour, compression, filter_method, interlace = header
+    if W < 1 or H < 1:
+        raise bad(f"empty image {W}x{H}")
+    if interlace != 0:
+        raise bad("interlaced (Adam7) files are not supported")
+    if colour == 4:
+        raise bad("colour type 4 (grey + alpha) is not supported (0 = grey, 2 = RGB, 3 = palette and 6 = RGBA only)")
+    if colour not in _ANY_CHANNELS:
+        raise bad(f"colour type {colour} is not supported (0 = grey, 2 = RGB, 3 = palette and 6 = RGBA only)")
+    if depth == 16:
+        raise bad("bit depth 16 is not supported (1, 2, 4 and 8 for grey and palette files, 8 for RGB and RGBA)")
+    if depth not in ((1, 2, 4, 8) if colour in (0, 3) else (8,)):
+        raise bad(f"bit depth {depth} is not supported for colour type {colour}")
+    if compression != 0 or filter_method != 0:
+        raise bad("unknown compression or filter method")
+    if colour == 3 and not palette:
+        raise bad("a palette file (colour type 3) without a PLTE chunk")
+    channels = _ANY_CHANNELS[colour]
+    row_bytes = (W * channels * depth + 7) // 8
+    return W, H, colour, depth, row_bytes, max(1, channels * depth // 8), _inflate_rows(bad, idat, H, row_bytes, "row bytes")
 
 
 def unfilter(filtered, B, W, H, channels):
-    """dgm_png_unfilter: `filtered` a uint8 device tensor of B * H * (1 + W * channels) bytes -> (B, H, W, channels) uint8."""
+    """dgm_png_unfilter: `filtered` a uint8 device tensor of B * H * (1 + W * channels) bytes -> (B, H, W, channels) uint8;
+    channels 1, 3 or 4 (the packed rows of a sub-byte image: W = the row's bytes, channels = 1)."""
     import torch
 
     from . import _lib
@@ -117,35 +167,86 @@ def unfilter(filtered, B, W, H, channels):
     return out
 
 
+def expand(packed, W, depth, scale):
+    """dgm_png_expand: packed (B, H, ceil(W * depth / 8)) uint8 on the device -> (B, H, W, 1) uint8, sample * scale."""
+    import torch
+
+    from . import _lib
+    if not (torch.is_tensor(packed) and packed.is_cuda and packed.dtype == torch.uint8 and packed.dim() == 3 and packed.is_contiguous()):
+        raise RuntimeError("expand needs a contiguous (B, H, row bytes) uint8 CUDA/HIP tensor (dg-mesh_amd has no CPU path for its kernels)")
+    B, H, rb = packed.shape
+    if depth not in (1, 2, 4, 8) or rb != (W * depth + 7) // 8:
+        raise ValueError(f"expand: rows of {rb} bytes for W={W} depth={depth}")
+    out = torch.empty((B, H, W, 1), dtype=torch.uint8, device=packed.device)
+    with _lib.device_guard(packed.device):
+        _lib.check(_lib.lib().dgm_png_expand(B, W, H, depth, scale, ctypes.c_void_p(packed.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                             _lib.stream_ptr()))
+    return out
+
+
+GREY_SCALE = {1: 255, 2: 85, 4: 17, 8: 1}  # Pillow's expansion of grey samples to 8 bits
+
+
+def mask_kind(colour, depth):
+    """What a mask file's bytes mean after decoding: "index" (palette indices, and 1-bit grey, which Pillow opens as mode 1: both
+    resize with NEAREST), "grey" (mode L), "rgb", "rgba"."""
+    if colour == 3 or (colour == 0 and depth == 1):
+        return "index"
+    return {0: "grey", 2: "rgb", 6: "rgba"}[colour]
+
+
+def _staged_groups(paths, device, parse, key_of, stride_of, who):
+    """parse the files on a thread pool, group them by key_of(parsed), stage each group in one page-locked buffer and upload it
+    once: yields (key, indices, device bytes of the group)."""
+    import torch
+    paths = list(paths)
+    if not paths:
+        raise ValueError(f"{who}: no files")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"{who} needs a CUDA/HIP device (dg-mesh_amd has no CPU path for its kernels)")
+    groups = {}
+    with ThreadPoolExecutor(max_workers=min(MAX_WORKERS, len(paths))) as pool:
+        parsed = list(pool.map(parse, paths))
+        for i, rec in enumerate(parsed):
+            groups.setdefault(key_of(rec), []).append(i)
+        for key, idx in groups.items():
+            # each file's scanlines are copied into their slot of the staging buffer once, by the pool
+            n = stride_of(key)
+            host = torch.empty(len(idx) * n, dtype=torch.uint8, pin_memory=True)
+            slots = host.numpy().reshape(len(idx), n)
+
+            def fill(k, i):
+                slots[k] = np.frombuffer(parsed[i][-1], np.uint8)
+                parsed[i] = None
+            list(pool.map(fill, range(len(idx)), idx))
+            yield key, idx, host.to(device)
+
+
+def decode_mask_groups(paths, device):
+    """decode_png_groups for mask files: a list of (indices, (n, H, W, C) uint8 batch, kind), one entry per (size, colour type,
+    bit depth).  kind as mask_kind; C is 1 for "index" and "grey", 3 and 4 for "rgb" and "rgba".  Grey samples are scaled to 8 bits
+    as Pillow scales them; palette indices are the indices."""
+    out = []
+    for (W, H, colour, depth, rb, bpp), idx, dev_bytes in _staged_groups(paths, device, parse_png_any, lambda r: r[:6],
+                                                                         lambda k: k[1] * (1 + k[4]), "decode_masks"):
+        if colour in (2, 6):
+            batch = unfilter(dev_bytes, len(idx), W, H, bpp)
+        else:
+            packed = unfilter(dev_bytes, len(idx), rb, H, 1).reshape(len(idx), H, rb)
+            batch = expand(packed, W, depth, GREY_SCALE[depth] if colour == 0 else 1)
+        out.append((idx, batch, mask_kind(colour, depth)))
+    return out
+
+
 def decode_png_groups(paths, device):
     """The files' pixels, grouped by (W, H, channels): a list of (indices, batch), `indices` the positions in `paths` of the
     files of one shape, in order, and `batch` their (len(indices), H, W, C) uint8 device tensor.  The files are inflated on a pool
     of at most MAX_WORKERS threads (zlib releases the GIL); each group has one page-locked staging buffer, one upload and one
     dgm_png_unfilter call."""
-    import torch
-    paths = list(paths)
-    if not paths:
-        raise ValueError("decode_pngs: no files")
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("decode_pngs needs a CUDA/HIP device (dg-mesh_amd has no CPU path for its kernels)")
-    groups, out = {}, []
-    with ThreadPoolExecutor(max_workers=min(MAX_WORKERS, len(paths))) as pool:
-        parsed = list(pool.map(parse_png, paths))
-        for i, (W, H, ch, _) in enumerate(parsed):
-            groups.setdefault((W, H, ch), []).append(i)
-        for (W, H, ch), idx in groups.items():
-            # each file's scanlines are copied into their slot of the staging buffer once, by the pool
-            n = H * (1 + W * ch)
-            host = torch.empty(len(idx) * n, dtype=torch.uint8, pin_memory=True)
-            slots = host.numpy().reshape(len(idx), n)
-
-            def fill(k, i):
-                slots[k] = np.frombuffer(parsed[i][3], np.uint8)
-                parsed[i] = None
-            list(pool.map(fill, range(len(idx)), idx))
-            out.append((idx, unfilter(host.to(device), len(idx), W, H, ch)))
-    return out
+    return [(idx, unfilter(dev_bytes, len(idx), W, H, ch))
+            for (W, H, ch), idx, dev_bytes in _staged_groups(paths, device, parse_png, lambda r: r[:3], lambda k: k[1] * (1 + k[0] * k[2]),
+                                                             "decode_pngs")]
 
 
 def decode_pngs(paths, device):

@@ -13,7 +13,13 @@ Pillow's Image.resize for 8 bits per channel, restated:
     divided by the sum when it is not zero; fixed point k = int(w 2^22 + 0.5), or int(w 2^22 - 0.5) for negative w;
   * an output byte is clamp((2^21 + sum pixel k) >> 22, 0, 255), int32 accumulator, arithmetic shift.
 `coefficients` is the host part (a few thousand libm calls per axis); `resize` runs the passes (dgm_resample, csrc/resample.hip).
-tests/golden/resample_small.npz pins the arithmetic against Pillow itself."""
+tests/golden/resample_small.npz pins the arithmetic against Pillow itself.
+
+Modes P and 1 (palette and bilevel images: the segmentation masks of real captures) are never filtered: Image.resize replaces any
+filter by NEAREST for them: an affine scaler whose source coordinate along an axis starts at 0.5 * in / out and grows by in / out per
+output pixel, both in float64, each index the running sum truncated (the sum, not the product (i + 0.5) * in / out: they differ
+where the product is an integer).  `nearest_indices` is that table, `resize_nearest` the gather (dgm_resample_nearest);
+tests/golden/capture_small.npz pins it against Pillow."""
 import ctypes
 import math
 
@@ -185,3 +191,55 @@ def resize(pixels, size, filter, premultiplied=None, out="bytes"):
         _lib.check(_lib.lib().dgm_resample(B, H, W, C, ptr(pixels), oh, ow, ptr(kx), ptr(bx), ksx, ptr(ky), ptr(by), ksy, flags, ptr(tmp),
                                            ptr(res), ptr(image), ptr(mask), _lib.stream_ptr()))
     return (image, mask) if planes else res
+
+
+def nearest_indices(in_size, out_size):
+    """One axis's NEAREST source indices as Pillow's affine scaler walks them: (out_size,) int32.  In float64, s = in_size / out_size;
+    the coordinate starts at 0.5 s and s is ADDED per output pixel; each index is the running sum truncated (at most in_size - 1).
+    The sum is not the product (i + 0.5) s: where that product is an integer the sum can lie just below it, and Pillow takes the
+    pixel before (8 -> 6, 270 -> 67, 536 -> 178 are such sizes)."""
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size < 1 or out_size < 1:
+        raise ValueError(f"nearest_indices: sizes must be positive, got {in_size} -> {out_size}")
+    scale = in_size / out_size
+    out = np.empty(out_size, np.int32)
+    xo = 0.5 * scale
+    for i in range(out_size):
+        out[i] = min(int(xo), in_size - 1)
+        xo += scale
+    return out
+
+
+_NEAREST = {}  # (in, out, device) -> the device table
+
+
+def _nearest_table(in_size, out_size, device):
+    import torch
+    key = (in_size, out_size, device.type, device.index if device.index is not None else torch.cuda.current_device())
+    if key not in _NEAREST:
+        _NEAREST[key] = torch.from_numpy(nearest_indices(in_size, out_size)).to(device)
+    return _NEAREST[key]
+
+
+def resize_nearest(pixels, size):
+    """Image.resize(size) of a batch of mode P / 1 images (any filter: Pillow uses NEAREST).  pixels: (B, H, W, C) uint8 on the
+    device, C 1, 3 or 4; size = (ow, oh) -> (B, oh, ow, C) uint8; an unchanged size returns `pixels` itself."""
+    import torch
+
+    from . import _lib
+    if not (torch.is_tensor(pixels) and pixels.is_cuda and pixels.dtype == torch.uint8 and pixels.dim() == 4 and pixels.shape[3] in (1, 3, 4)):
+        raise RuntimeError("resize_nearest needs a (B, H, W, 1, 3 or 4) uint8 CUDA/HIP tensor (dg-mesh_amd has no CPU path for its kernels)")
+    B, H, W, C = pixels.shape
+    ow, oh = (int(v) for v in size)
+    if ow < 1 or oh < 1:
+        raise ValueError(f"resize_nearest: size must be positive, got {(ow, oh)}")
+    if (ow, oh) == (W, H):
+        return pixels
+    pixels = pixels.contiguous()
+    dev = pixels.device
+    xs, ys = _nearest_table(W, ow, dev), _nearest_table(H, oh, dev)
+    out = torch.empty((B, oh, ow, C), dtype=torch.uint8, device=dev)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+    with _lib.device_guard(dev):
+        _lib.check(_lib.lib().dgm_resample_nearest(B, H, W, C, ptr(pixels), oh, ow, ptr(xs), ptr(ys), ptr(out), _lib.stream_ptr()))
+    return out

@@ -8,8 +8,10 @@ the loop, logs the losses without a per-step host wait, writes checkpoints and s
 
 Configuration: the defaults of ModelParams (below), scene.OptimizationParams, scene.PipelineParams and DRIVER_DEFAULTS; a flat YAML
 file over them; `--key value` command-line overrides over that.  An unknown key is an error that lists every unknown key; the keys
-of IGNORED_KEYS, which the reference defines and this project has no use for, are dropped with one log line.  The merged dict is
-written to model_path/cfg_args.txt.
+of IGNORED_KEYS, which the reference defines and this project has no use for, are dropped with one log line; the reference's
+gaussian_center is read as the driver's dpsr_center (TRANSLATED_KEYS).  The merged dict is written to model_path/cfg_args.txt.
+
+Scenes: Blender / D-NeRF directories, and with data_type Nerfies, iPhone or NeuralActor the real captures of captures.py.
 
 LPIPS of the test views (--lpips_alex FILE, --lpips_vgg FILE): weight files in any layout lpips.py reads; the project ships none.
 With either, testing() also reports LPIPS_A / LPIPS_V; without, the run is what it was.
@@ -36,6 +38,7 @@ class ModelParams:
     is_6dof = False
     data_type = ""
     downsample = 1.0
+    nerfies_ratio = 0.5
     resolution = -1
     prune_threshold = 0.005
     laplacian_loss_weight = 1.0
@@ -47,10 +50,12 @@ class ModelParams:
 
 # the driver's own switches (R/train.py:858-886 argparse flags)
 DRIVER_DEFAULTS = {"config": None, "start_checkpoint": None, "log_every": 1000, "save_iterations": None, "checkpoint_iterations": None,
-                   "seed": 0, "quiet": False, "lpips_alex": None, "lpips_vgg": None}
+                   "seed": 0, "quiet": False, "lpips_alex": None, "lpips_vgg": None, "dpsr_center": None}
+# the reference's gaussian_center is read under the driver's own name: only real captures -- iPhone, NeuralActor -- place the DPSR cube
+# by it (R/scene/gaussian_model_dpsr_dynamic_anchor.py:686-689); the other data types measure their Gaussians and never look at it
+TRANSLATED_KEYS = {"gaussian_center": ("dpsr_center", "the DPSR cube's centre for iPhone / NeuralActor captures")}
 # defined by the reference's parameter groups or command line, unused here
-# (gaussian_center: only real captures -- iPhone, NeuralActor -- place the DPSR cube by it; their readers are not built)
-IGNORED_KEYS = ("gaussian_center", "expname", "images", "data_device", "data_mask", "load2gpu_on_the_fly", "nerfies_ratio", "save_wis3d",
+IGNORED_KEYS = ("expname", "images", "data_device", "data_mask", "load2gpu_on_the_fly", "save_wis3d",
                 "pretrain_mesh_path", "pretrain_mesh_path_test", "pretrained_type", "first_iter", "ip", "port", "detect_anomaly",
                 "test_iterations")
 PARAM_CLASSES = (ModelParams, S.OptimizationParams, S.PipelineParams)
@@ -70,9 +75,12 @@ def default_config():
 def merge_config(*layers, log=print):
     """default_config() with each dict of `layers` merged over it in turn.  ValueError listing every unknown key."""
     cfg = default_config()
-    unknown, ignored = [], []
+    unknown, ignored, translated = [], [], []
     for layer in layers:
         for k, v in (layer or {}).items():
+            if k in TRANSLATED_KEYS:
+                k = TRANSLATED_KEYS[k][0]
+                translated.append(k)
             if k in cfg:
                 cfg[k] = v
             elif k in IGNORED_KEYS:
@@ -85,8 +93,13 @@ def merge_config(*layers, log=print):
     for k in LIST_KEYS:
         if cfg[k] is not None:
             cfg[k] = iteration_list(k, cfg[k])
+    if cfg["dpsr_center"] is not None:
+        cfg["dpsr_center"] = center_triple("dpsr_center", cfg["dpsr_center"])
     if unknown:
         raise ValueError(f"unknown configuration key(s): {', '.join(sorted(set(unknown)))}")
+    for old, (new, why) in TRANSLATED_KEYS.items():
+        if new in translated:
+            log(f"[config] {old} -> {new} ({why})")
     if ignored:
         log(f"[config] ignored (defined by the reference, unused here): {', '.join(sorted(set(ignored)))}")
     return cfg
@@ -113,6 +126,15 @@ def iteration_list(key, value):
     return sorted(set(items))
 
 
+def center_triple(key, value):
+    """Three finite numbers as a list of floats."""
+    ok = isinstance(value, (list, tuple)) and len(value) == 3 and all(
+        isinstance(v, (int, float)) and not isinstance(v, bool) and v == v and abs(v) != float("inf") for v in value)
+    if not ok:
+        raise ValueError(f"{key}: expected three numbers [x, y, z], got {value!r}")
+    return [float(v) for v in value]
+
+
 def _coerce(key, text, default):
     """A command-line string as the type of the key's default (None defaults: YAML's own reading of the string)."""
     import yaml
@@ -121,6 +143,8 @@ def _coerce(key, text, default):
     value = yaml.safe_load(text)
     if key in LIST_KEYS:
         return iteration_list(key, value)
+    if key == "dpsr_center":
+        return center_triple(key, value)
     if isinstance(value, str) and isinstance(default, (int, float)) and not isinstance(default, bool):
         try:  # (YAML 1.1 reads 1e-4 as a string)
             value = float(text)
@@ -193,14 +217,14 @@ def _loss_logging_trainer():
     return LoggingTrainer
 
 
-def mesh_phase_options(lp, op, seed=0):
+def mesh_phase_options(lp, op, seed=0, center=None):
     """The MeshPhase arguments the driver derives from the configuration (the networks, the DPSR module and the device aside).
     real: the reference places the DPSR cube by gaussian_ratio / gaussian_center alone only for the iPhone and NeuralActor data types
     (R/scene/gaussian_model_dpsr_dynamic_anchor.py:686-689) and measures the deformed Gaussians for every other one, whatever
-    is_blender says; the readers built here are of the second kind."""
+    is_blender says.  center: the configuration's dpsr_center, the cube's centre for those two (None: the origin)."""
     return dict(seed=seed, mesh_source="diffmc", mesh_losses="render", laplacian_loss_weight=lp.laplacian_loss_weight,
                 anchor=op.use_anchor > 0, normal_init=True, gaussian_ratio=lp.gaussian_ratio,
-                real=getattr(lp, "data_type", "") in ("iPhone", "NeuralActor"))
+                real=getattr(lp, "data_type", "") in ("iPhone", "NeuralActor"), gaussian_center=center)
 
 
 LOG_COLUMNS = ("loss", "img_loss", "cycle_loss", "mask_loss", "mesh_img_loss", "laplacian_loss", "anchor_loss")
@@ -251,7 +275,8 @@ def training(cfg, *, gaussians=None, networks=None, log=print):
                          D.DeformModelNormalSep(is_blender=lp.is_blender, is_6dof=lp.is_6dof, model_name="deform_back_normal", device=dev,
                                                 trunk_impl=impl),
                          D.AppearanceModel(is_blender=lp.is_blender, device=dev, trunk_impl=impl),
-                         dpsr=DP.DPSR(res=(int(lp.grid_res),) * 3, sig=lp.dpsr_sig), device=dev, **mesh_phase_options(lp, op, seed))
+                         dpsr=DP.DPSR(res=(int(lp.grid_res),) * 3, sig=lp.dpsr_sig), device=dev,
+                         **mesh_phase_options(lp, op, seed, cfg["dpsr_center"]))
     nets = {m.model_name: m for m in [deform, deform_back] + (mesh.networks() if mesh is not None else [])}
     if start:
         gaussians.load_ply(start, iteration=first_iter)

@@ -147,7 +147,8 @@ class MeshPhase:
 
     def __init__(self, deform_normal, deform_back_normal, appearance, dpsr=None, n_verts=20000, density_thres=None,
                  center=None, scale=None, seed=0, device="cuda", stand_in_weight=1e-6, mesh_source="probes",
-                 laplacian_loss_weight=1.0, mesh_losses="stand_in", *, anchor=False, normal_init=False, gaussian_ratio=1.1, real=False):
+                 laplacian_loss_weight=1.0, mesh_losses="stand_in", *, anchor=False, normal_init=False, gaussian_ratio=1.1, real=False,
+                 gaussian_center=None):
         if mesh_source not in ("probes", "diffmc"):
             raise ValueError(f"MeshPhase: mesh_source must be 'probes' or 'diffmc', got {mesh_source!r}")
         if mesh_losses not in ("stand_in", "render"):
@@ -162,7 +163,11 @@ class MeshPhase:
         self.anchor = bool(anchor)
         # normal_initialization at iteration == dpsr_iter (normal_init.py); gaussian_ratio / real: the dataset's gaussian_ratio and
         # whether it is a real capture (R/...:686-689); out_dir: where mesh_init.ply / pointcloud_init.ply go (None: not written)
+        # gaussian_center: where a real capture's cube sits (None: the origin); unused with real=False
         self.normal_init, self.gaussian_ratio, self.real = bool(normal_init), float(gaussian_ratio), bool(real)
+        self.gaussian_center = (0.0, 0.0, 0.0) if gaussian_center is None else tuple(float(v) for v in gaussian_center)
+        if len(self.gaussian_center) != 3:
+            raise ValueError(f"MeshPhase: gaussian_center must be three numbers, got {gaussian_center!r}")
         self.normal_init_out_dir = None
         self.last_normal_init = None  # normal_initialization's result (V, F, verts, faces, ...)
         self.last_anchor = None  # (verts, faces, fid) of the latest anchoring event
@@ -368,6 +373,7 @@ class Trainer:
         det = lambda v: v.detach() if torch.is_tensor(v) else v
         ms.last_normal_init = normal_initialization(
             g, self.deform, det(d_xyz), det(d_rotation), det(d_scaling), opt=self.opt, gaussian_ratio=ms.gaussian_ratio, real=ms.real,
+            gaussian_center=ms.gaussian_center,
             generator=self.normal_init_generator, out_dir=ms.normal_init_out_dir if self.rank == 0 else None, diffmc=ms.diffmc)
         self._area_check = ms.last_normal_init["area_check"]  # inspected at the start of the next step(): no wait here
         if self.world > 1:

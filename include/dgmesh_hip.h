@@ -58,7 +58,9 @@ extern "C" {
  *      dgm_tri_* (mesh rasterizer), dgm_anchor_* (Gaussian-mesh anchoring), dgm_ninit_* (entering the mesh phase),
  *      dgm_image_metrics* (test-view metrics), dgm_vertex_normals / dgm_mesh_shade / dgm_point_splat* / dgm_compose_frame
  *      (rendering a checkpoint), dgm_emd_* (mesh evaluation), dgm_png_unfilter / dgm_image_ingest (reading a dataset),
- *      dgm_image_composite_bytes / dgm_resample (resizing a dataset's images), dgm_lpips* (LPIPS of the test views). */
+ *      dgm_image_composite_bytes / dgm_resample (resizing a dataset's images), dgm_lpips* (LPIPS of the test views),
+ *      dgm_png_expand / dgm_image_ingest_masked / dgm_resample_nearest (real captures: mask PNGs and masked frames); dgm_png_unfilter
+ *      also takes channels = 1. */
 #define DGM_ABI_VERSION 5
 
 /* Allocator callback: must return a device pointer to at least `bytes` bytes (128-byte aligned),
@@ -641,17 +643,33 @@ int dgm_emd_approx(int b, int n, int m, const float* xyz1, const float* xyz2, fl
  * Replaces PIL's decoder and the numpy compositing of readCamerasFromTransforms + PILtoTorch (dgmesh/scene/dataset_readers.py:288-302,
  * dgmesh/utils/general_utils.py:23-29).  Every buffer but bg3 is device memory; nothing is allocated and nothing is read back.
  *   dgm_png_unfilter: `filtered` holds B inflated IDAT streams of 8-bit, non-interlaced images of one W, H and channels (3: colour type
- *       2, 4: colour type 6), back to back: each H rows of 1 + W channels bytes, the first byte of a row its filter type 0..4 (None,
+ *       2, 4: colour type 6, 1: 8-bit grey or palette, or the packed rows of a 1-, 2- or 4-bit image with W = the row's bytes, whose
+ *       filters work on bytes), back to back: each H rows of 1 + W channels bytes, the first byte of a row its filter type 0..4 (None,
  *       Sub, Up, Average with floor((a + b) / 2), Paeth with the specification's tie order; arithmetic mod 256 per byte, neighbours
- *       `channels` bytes apart).  out (B, H, W, channels) uint8, 4-byte aligned.  A filter type above 4 is read as 0: the caller checks
+ *       `channels` bytes apart).  out (B, H, W, channels) uint8, 4-byte aligned unless channels is 1.  A filter type above 4 is read as 0: the caller checks
  *       the type bytes before the upload.  One workgroup per image, one lane per row, rows skewed by one pixel; the trip counts are
  *       uniform and no thread waits on memory.  1 <= W, H <= 2^24; offsets are 64-bit.
  *   dgm_image_ingest: in (B, H, W, C) uint8, C 3 or 4 (C = 3: alpha 255); bg3 a HOST array of three floats.  In fp64 and in this
  *       order, without contraction: n = byte / 255.0, v = (n_c n_a + bg (1 - n_a)) 255.0, q = v truncated to a byte; then
  *       image (B, 3, H, W) = (float)q / 255.0f correctly rounded, and mask (B, H, W, 1) = (float)n_a.  1 <= B <= 65535.  image and
- *       mask are 4-byte aligned; `in` is 4-byte aligned for C = 4 and may start at any byte for C = 3. */
+ *       mask are 4-byte aligned; `in` is 4-byte aligned for C = 4 and may start at any byte for C = 3.
+ *   dgm_png_expand: packed (B, H, ceil(W depth / 8)) bytes, the unfiltered rows of a grey or palette image of bit depth 1, 2, 4 or 8
+ *       -> out (B, H, W) bytes, one per pixel: the sample (most significant bits first; a row's padding bits are not read) times
+ *       `scale`.  Pillow scales grey samples by 255, 85, 17, 1 for depths 1, 2, 4, 8 and leaves palette indices alone (scale 1);
+ *       scale (2^depth - 1) <= 255.  1 <= B <= 65535.
+ *   dgm_image_ingest_masked: the real captures' compositing (readNerfiesCameras / readiPhoneCameras / readNeuralActorCameras,
+ *       dgmesh/scene/dataset_readers.py:545-865).  in (B, H, W, C) uint8, C 3 or 4 (a fourth channel is dropped); mask (B, H, W, Cm)
+ *       uint8, Cm 1, 3 or 4, of which channel 0 counts: m = mask[..., 0] > 0.  q_c = m ? in_c : the background byte, which is
+ *       dgm_image_ingest's q for alpha 0 (255 bg truncated).  flags 0: image (B, 3, H, W) = (float)q / 255.0f correctly rounded,
+ *       alpha (B, H, W, 1) = m as 0 / 1; bytes_out unused.  DGM_INGEST_BYTES: bytes_out (B, H, W, 4) = (q_R, q_G, q_B, 255 m), the
+ *       input of a `resolution` resize (dgm_resample with DGM_RESAMPLE_PLANES); image and alpha unused.  The unused outputs may be NULL.
+ *       Outputs 4-byte aligned; `in` 4-byte aligned for C = 4; mask at any byte. */
+#define DGM_INGEST_BYTES 1
 int dgm_png_unfilter(int B, int W, int H, int channels, const unsigned char* filtered, unsigned char* out, void* stream);
 int dgm_image_ingest(int B, int H, int W, int C, const unsigned char* in, const float* bg3, float* image, float* mask, void* stream);
+int dgm_png_expand(int B, int W, int H, int depth, int scale, const unsigned char* packed, unsigned char* out, void* stream);
+int dgm_image_ingest_masked(int B, int H, int W, int C, const unsigned char* in, int Cm, const unsigned char* mask, const float* bg3, int flags,
+                            float* image, float* alpha, unsigned char* bytes_out, void* stream);
 
 /* ---- image resampling: Pillow's 8-bit Image.resize on the device (csrc/resample.hip, csrc/ingest.hip) -----------------------------
  * Replaces image.resize(..., LANCZOS) of readCamerasFromTransforms (dgmesh/scene/dataset_readers.py:289) and the bicubic
@@ -674,13 +692,19 @@ int dgm_image_ingest(int B, int H, int W, int C, const unsigned char* in, const 
  *       otherwise min(255, 255 c' / a) in integers.  DGM_RESAMPLE_PLANES (C = 3 or 4): the last pass writes image (B, 3, oh, ow) =
  *       (float) byte / 255.0f, correctly rounded, and mask (B, oh, ow, 1) = (float) ((double) a / 255.0) (1 for C = 3) instead of
  *       out_bytes (B, oh, ow, C).  The unused one of out_bytes and (image, mask) may be NULL.  in, tmp and out_bytes are 4-byte
- *       aligned for C = 4 and may start at any byte otherwise; image and mask are 4-byte aligned. */
+ *       aligned for C = 4 and may start at any byte otherwise; image and mask are 4-byte aligned.
+ *   dgm_resample_nearest: Pillow's NEAREST, which Image.resize substitutes for any filter on modes P and 1: out (B, oh, ow, C) =
+ *       in[b][ys[y]][xs[x]], xs (ow) and ys (oh) int32 device tables of source indices, computed on the host as Pillow's affine
+ *       scaler walks an axis (resample.nearest_indices): in float64 the coordinate starts at 0.5 in / out, in / out is added per output
+ *       pixel, and each index is the running sum truncated; indices are clamped into the image.  C 1, 3 or 4; sizes as dgm_resample. */
 #define DGM_RESAMPLE_PREMULTIPLIED 1
 #define DGM_RESAMPLE_PLANES 2
 int dgm_image_composite_bytes(int B, int H, int W, int C, const unsigned char* in, const float* bg3, unsigned char* out, void* stream);
 int dgm_resample(int B, int H, int W, int C, const unsigned char* in, int oh, int ow, const int* kx, const int* bounds_x, int ksize_x,
                  const int* ky, const int* bounds_y, int ksize_y, int flags, unsigned char* tmp, unsigned char* out_bytes, float* image,
                  float* mask, void* stream);
+int dgm_resample_nearest(int B, int H, int W, int C, const unsigned char* in, int oh, int ow, const int* xs, const int* ys,
+                         unsigned char* out, void* stream);
 
 #ifdef __cplusplus
 }
