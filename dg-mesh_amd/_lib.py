@@ -33,6 +33,12 @@ class MlpParams(_c.Structure):
         ("W", _vp * 8), ("b", _vp * 8), ("Wh", _vp), ("bh", _vp)]
 
 
+class MlpBackwardJob(_c.Structure):
+    """Mirror of dgm_mlp_backward_job (include/dgmesh_hip.h)."""
+    _fields_ = [("params", _c.POINTER(MlpParams)), ("dOut", _vp), ("workspace", _vp), ("dW", _vp * 8), ("db", _vp * 8),
+                ("dWh", _vp), ("dbh", _vp), ("dtemb", _vp)]
+
+
 # name -> (restype, argtypes); must list every symbol declared in include/dgmesh_hip.h
 _f, _i = _c.c_float, _c.c_int
 SYMBOLS = {
@@ -141,8 +147,10 @@ SYMBOLS = {
     "dgm_mlp_workspace_bytes": (_c.c_size_t, [_i]),
     "dgm_mlp_describe_workspace": (_i, [_i, _c.POINTER(_c.c_size_t), _i]),
     "dgm_mlp_forward": (_i, [_c.POINTER(MlpParams), _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "dgm_mlp_forward_add": (_i, [_c.POINTER(MlpParams), _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     "dgm_mlp_backward": (_i, [_c.POINTER(MlpParams), _i, _vp, _i, _vp, _vp * 8, _vp * 8, _vp, _vp, _vp, _vp]),
     "dgm_mlp_backward_dx": (_i, [_c.POINTER(MlpParams), _i, _vp, _i, _vp, _vp * 8, _vp * 8, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_mlp_backward_group": (_i, [_c.POINTER(MlpBackwardJob), _c.POINTER(MlpBackwardJob), _i, _i, _vp]),
 }
 
 _LIB = None

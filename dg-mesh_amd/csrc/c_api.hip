@@ -86,6 +86,7 @@ struct EventPair {
 };
 constexpr int kMaxDeferred = 4096;
 EventPair g_deferred[DGM_STAGE_COUNT][kMaxDeferred];
+int g_deferred_w[DGM_STAGE_COUNT][kMaxDeferred];  // units of the stage inside the bracket (1, or 2 for a grouped MLP launch)
 int g_deferred_n[DGM_STAGE_COUNT] = {0};
 int g_deferred_created[DGM_STAGE_COUNT] = {0};
 // sampling: only every g_sample_every-th launch of a stage is bracketed (two hipEventRecord per bracket cost host time
@@ -134,6 +135,7 @@ struct StageTimer {
                 (void)hipEventCreate(&g_deferred[s][i].b);
                 g_deferred_created[s] = i + 1;
             }
+            g_deferred_w[s][i] = 1;
             (void)hipEventRecord(g_deferred[s][i].a, st);
             used[s] = true;
         }
@@ -163,13 +165,18 @@ struct StageTimer {
 
 namespace dgm {
 // deferred-mode stage brackets for translation units without a StageTimer (mlp.hip); no-ops unless mode == 2
-void prof_begin(int s, hipStream_t st) {
+// passes: the launch carries that many of the stage's units (a grouped launch serves two networks): it counts as `passes` launches
+// and its time is shared among them, so a stage's average stays the price of ONE unit
+void prof_begin(int s, hipStream_t st, int passes) {
     if (g_profile != 2) return;
     std::lock_guard<std::mutex> lk(g_prof_mu);
     g_open[s] = false;
-    if ((g_calls[s]++ % g_sample_every) != 0 || g_deferred_n[s] >= kMaxDeferred) return;
+    const bool sampled = (g_calls[s] % g_sample_every) < passes;
+    g_calls[s] += passes;
+    if (!sampled || g_deferred_n[s] >= kMaxDeferred) return;
     g_open[s] = true;
     const int i = g_deferred_n[s];
+    g_deferred_w[s][i] = passes;
     if (i >= g_deferred_created[s]) {
         (void)hipEventCreate(&g_deferred[s][i].a);
         (void)hipEventCreate(&g_deferred[s][i].b);
@@ -231,7 +238,7 @@ int dgm_collect_stage_ms(float* avg_ms, int* counts, int capacity) {
             float ms = 0;
             if (hipEventElapsedTime(&ms, g_deferred[s][i].a, g_deferred[s][i].b) == hipSuccess) {
                 tot += ms;
-                ok++;
+                ok += g_deferred_w[s][i];
             }
         }
         avg_ms[s] = ok ? (float)(tot / ok) : 0.f;

@@ -333,13 +333,15 @@ struct ReduceDwJob {
 };
 struct ReduceDwBatch {
     int emb_dim, n_jobs;
-    ReduceDwJob job[9];
-    // blockIdx.y == n_jobs: the heads' partial sums (mlp_heads_bwd_kernel) ride along, see reduce_heads_body
-    int h_chunks, h_bchunks, h_nout;  // (h_bchunks: rows of h_partial_b -- the plane path leaves one per 32-row tile)
-    const float* h_partial_W;
-    const float* h_partial_b;
-    float* h_dW;
-    float* h_db;
+    ReduceDwJob job[18];  // (nine per network: a grouped backward pass reduces two networks in one launch)
+    // blockIdx.y >= n_jobs: the heads' partial sums (mlp_heads_bwd_kernel) ride along, see reduce_heads_body; one set per network
+    struct Heads {
+        int chunks, bchunks, nout;  // (bchunks: rows of partial_b -- the plane path leaves one per 32-row tile)
+        const float* partial_W;
+        const float* partial_b;
+        float* dW;
+        float* db;
+    } heads[2];
 };
 __device__ __forceinline__ void reduce_heads_body(int bx, int o, int chunks, int bchunks, const float* __restrict__ partial_W,
                                                   const float* __restrict__ partial_b, float* __restrict__ dWh,
@@ -364,9 +366,10 @@ mlp_reduce_dw_all_kernel(const ReduceDwBatch rb) {
     constexpr int KT = RDW_KT, JT = RDW_JT, JQ = JT / 4, JB = MLP_W / JT;
     __shared__ float4 red[4][64];
     __shared__ float redb[32][8];
-    if ((int)blockIdx.y == rb.n_jobs) {  // (workgroup-uniform branch)
-        if ((int)blockIdx.x < 8 * rb.h_nout)
-            reduce_heads_body(blockIdx.x & 7, blockIdx.x >> 3, rb.h_chunks, rb.h_bchunks, rb.h_partial_W, rb.h_partial_b, rb.h_dW, rb.h_db);
+    if ((int)blockIdx.y >= rb.n_jobs) {  // (workgroup-uniform branch)
+        const ReduceDwBatch::Heads& h = rb.heads[(int)blockIdx.y - rb.n_jobs];
+        if ((int)blockIdx.x < 8 * h.nout)
+            reduce_heads_body(blockIdx.x & 7, blockIdx.x >> 3, h.chunks, h.bchunks, h.partial_W, h.partial_b, h.dW, h.db);
         return;
     }
     const ReduceDwJob& jb = rb.job[blockIdx.y];
@@ -704,7 +707,7 @@ using namespace dgm;
 
 namespace dgm {
 void set_last_error(const char* msg);  // c_api.hip
-void prof_begin(int stage, hipStream_t st);
+void prof_begin(int stage, hipStream_t st, int passes = 1);
 void prof_end(int stage, hipStream_t st);
 }
 namespace {
@@ -949,7 +952,7 @@ int p4_pair_split(int ntiles, int gx) {
 // fold: one time value per call (temb_stride == 0) on round 6's kernel forms -- the embedding is 64 columns wide, the time row sits
 // in the biases of layer 0 and the skip layer, the skip layer is one K = 320 GEMM (no `Cin`), the 256-wide layers run one wave per SIMD.
 int forward_planes(const dgm_mlp_params* p, int N, const float* x, const float* temb, int temb_stride, const Ws& w, float* out,
-                   hipStream_t st, const bool fold, const bool all5) {
+                   hipStream_t st, const bool fold, const bool all5, const float* xadd = nullptr, const int xadd_stride = 0) {
     const P4Plan pl = p4_plan(N);
     const int nt = pl.ntiles, gx = nt < num_cus() ? nt : num_cus();
     const int sk = p->skip_layer;
@@ -966,7 +969,7 @@ int forward_planes(const dgm_mlp_params* p, int N, const float* x, const float* 
     am.job[8].W = p->Wh, am.job[8].n = p->n_out * MLP_W;
     if (!fold)
         hipLaunchKernelGGL(mlp_embed4_kernel, dim3(nt + 8 * am.n_jobs), dim3(256), 0, st, N, nt, x, temb, temb_stride, p->t_dim,
-                           (unsigned char*)w.emb, w.Eexp, am, w.matmax, EW);
+                           (unsigned char*)w.emb, w.Eexp, am, w.matmax, EW, xadd, xadd_stride);
     if (fold) {  // every weight matrix as two binary16 planes, one power-of-two scale per OUTPUT COLUMN, biases pre-scaled
         Prep4cBatch pc;
         int nc = 0;
@@ -990,10 +993,10 @@ int forward_planes(const dgm_mlp_params* p, int N, const float* x, const float* 
         static const bool merged = [] { const char* e = getenv("DGM_MLP_EMBED_MERGED"); return !(e && atoi(e) == 0); }();
         if (merged) {
             const int n_prep = (MLP_W / P4C_COLS) * nc;
-            hipLaunchKernelGGL(mlp_embed4c_kernel, dim3(n_prep + nt), dim3(256), 0, st, N, x, (unsigned char*)w.emb, w.Eexp, EW, pc, n_prep);
+            hipLaunchKernelGGL(mlp_embed4c_kernel, dim3(n_prep + nt), dim3(256), 0, st, N, x, (unsigned char*)w.emb, w.Eexp, EW, pc, n_prep, xadd, xadd_stride);
         } else {
             hipLaunchKernelGGL(mlp_embed4_kernel, dim3(nt), dim3(256), 0, st, N, nt, x, temb, temb_stride, p->t_dim,
-                               (unsigned char*)w.emb, w.Eexp, am, w.matmax, EW);
+                               (unsigned char*)w.emb, w.Eexp, am, w.matmax, EW, xadd, xadd_stride);
             hipLaunchKernelGGL(mlp_prep4c_kernel, dim3(MLP_W / P4C_COLS, nc), dim3(256), 0, st, pc);
         }
     }
@@ -1237,8 +1240,8 @@ int backward_planes(const dgm_mlp_params* p, int N, const float* dOut, int temb_
     // (tried: each layer's reduction on a side stream under the next layer's launch -- its small workgroups do fit beside a
     // resident pair workgroup -- 265 vs 274 it/s: slower, the pair kernel's HBM-bound half gets the competition)
     rb.n_jobs = n_pending;
-    rb.h_chunks = pl.chunks, rb.h_bchunks = nt, rb.h_nout = p->n_out, rb.h_partial_W = w.partial_h, rb.h_partial_b = w.partial_hb;
-    rb.h_dW = dWh, rb.h_db = dbh;
+    rb.heads[0].chunks = pl.chunks, rb.heads[0].bchunks = nt, rb.heads[0].nout = p->n_out;
+    rb.heads[0].partial_W = w.partial_h, rb.heads[0].partial_b = w.partial_hb, rb.heads[0].dW = dWh, rb.heads[0].db = dbh;
     hipLaunchKernelGGL(mlp_reduce_dw_all_kernel, dim3(rb_blocks, rb.n_jobs + 1), dim3(256), 0, st, rb);
     if (fold) {  // the time columns of dW_0 / dW_skip: db (x) t_emb; and dL/dt_emb (one launch)
         FoldGradArgs f;
@@ -1249,6 +1252,174 @@ int backward_planes(const dgm_mlp_params* p, int N, const float* dOut, int temb_
     } else if (dtemb != nullptr && !per_row_t)
         hipLaunchKernelGGL(mlp_dtemb_bcast_kernel, dim3(p->t_dim), dim3(256), 0, st, p->t_dim, db[0], p->W[0], layer_in(p, 0),
                            db[sk], p->W[sk], layer_in(p, sk), dtemb);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return mlp_fail(hipGetErrorString(e));
+    return 0;
+}
+
+// ---- two networks' backward passes in shared launches (dgm_mlp_backward_group) -----------------------------------------------------
+// The folded f16x3p forms with the paired launches only (the caller falls back to two ordinary passes otherwise).  Layers 7 .. 0
+// are walked once; every launch of backward_planes() appears once and serves both networks (the group kernels of
+// mlp_planes.hpp).  The row chunks of every weight gradient, their partial tiles and the reduction's jobs are those of
+// backward_planes(): the gradients are bit-identical to two ordinary passes.  What the grouping saves is launches (eleven per
+// step), the layer GEMM's weight prologue per tile, and the tail of a launch whose tiles do not divide by its workgroups.
+struct GroupNet {
+    const dgm_mlp_params* p;
+    const float* dOut;
+    Ws w;
+    float* const* dW;
+    float* const* db;
+    float *dWh, *dbh, *dtemb;
+};
+// weight-gradient chunks per network of a paired launch, as backward_planes() has them; 0 = pairing off
+int p4_pair_chunks(int N) {
+    const P4Plan pl = p4_plan(N);
+    const int nt = pl.ntiles, gx = nt < num_cus() ? nt : num_cus();
+    int n_dw = p4_pair_split(nt, gx);
+    if (n_dw > pl.chunks) n_dw = pl.chunks;
+    return n_dw;
+}
+// workgroups per role and network of a grouped paired launch: half of the chunks, a multiple of 8; 0 = no grouping
+int p4_group_split(int N) {
+    const P4Plan pl = p4_plan(N);
+    const int nt = pl.ntiles, gx = nt < num_cus() ? nt : num_cus();
+    const int n_wg = (p4_pair_chunks(N) / 2) & ~7;
+    if (n_wg < 8 || 4 * n_wg > gx) return 0;
+    return n_wg;
+}
+int backward_planes_group(const GroupNet* nets, int N, const int n_wg, hipStream_t st) {
+    const P4Plan pl = p4_plan(N);
+    const int nt = pl.ntiles, sk = 5, EW = 64;
+    const int n_dw = p4_pair_chunks(N);                      // a network's weight-gradient chunks, as in backward_planes()
+    const int cpw = (n_dw + n_wg - 1) / n_wg;                // ... of which a workgroup runs this many
+    const int tpc_s = pl.tiles_per_chunk, chunks_s = pl.chunks;  // stand-alone weight-gradient launches: backward_planes()'s chunks, blockIdx.y = network
+    const int tpc_pair = (nt + n_dw - 1) / n_dw, chunks_pair = (nt + tpc_pair - 1) / tpc_pair;  // (the last few chunks may have no tile and write none)
+    {
+        Dout4GroupArgs da;
+        for (int i = 0; i < 2; i++)
+            da.NC[i] = nets[i].p->n_out, da.dOut[i] = nets[i].dOut, da.Dp[i] = nets[i].w.Dp, da.Dexp[i] = nets[i].w.Dexp, da.partial_b[i] = nets[i].w.partial_hb;
+        hipLaunchKernelGGL(mlp_dout4_group_kernel, dim3((nt + 3) / 4, 2), dim3(256), 0, st, N, nt, da);
+    }
+    unsigned char *G[2], *Gn[2];
+    int *Ge[2], *Gne[2];
+    PairGroupArgs pg;
+    memset(&pg, 0, sizeof(pg));
+    for (int i = 0; i < 2; i++) {
+        const Ws& w = nets[i].w;
+        G[i] = (unsigned char*)w.Ga, Gn[i] = (unsigned char*)w.Gb, Ge[i] = w.Gexp[0], Gne[i] = w.Gexp[1];
+        pg.ga[i].ntiles = nt, pg.ga[i].M = N, pg.ga[i].exps_limit = p4_exps_limit();
+        pg.da[i].ntiles = nt;
+    }
+    {   // G_7 = (dOut Wh) masked by layer 7's ReLU: two workgroups per CU in all, as in backward_planes()
+        Gemm4GroupArgs g7a;
+        for (int i = 0; i < 2; i++) {
+            const Ws& w = nets[i].w;
+            Gemm4Args& a = g7a.a[i];
+            a = pg.ga[i];
+            a.A = w.Dp, a.Aexp = w.Dexp, a.Bp = w.Wh4b, a.b_inv = w.wsc_hb, a.mask_in = w.mask[7], a.C = G[i], a.Cexp = Ge[i];
+        }
+        const int g7 = nt < num_cus() ? nt : num_cus();
+        static bool done_[DGM_MAX_DEVICES] = {false};
+        if (p4_lds_attr(mlp_gemm4_group_kernel<1, 128, 64, 1, false, 8, true>, CfgG7C::LDS, &done_[current_device_slot()]) != hipSuccess)
+            return mlp_fail("mlp: cannot raise the LDS limit of a plane-path kernel");
+        hipLaunchKernelGGL((mlp_gemm4_group_kernel<1, 128, 64, 1, false, 8, true>), dim3(g7, 2), dim3(512), CfgG7C::LDS, st, g7a);
+    }
+    Dw4GroupArgs dg;
+    memset(&dg, 0, sizeof(dg));
+    {   // heads' weight gradient: dWh[o][c] = sum_r dOut[r][o] Y7[r][c]
+        for (int i = 0; i < 2; i++) {
+            const Ws& w = nets[i].w;
+            Dw4Args& d = dg.a[i];
+            d.ntiles = nt, d.tiles_per_chunk = tpc_s;
+            d.X = (const unsigned char*)w.Y[7], d.Xexp = w.Yexp[7], d.G = w.Dp, d.Gexp = w.Dexp, d.partial = w.partial_h, d.chunk_stride = 0;
+            d.partial_db = nullptr;
+        }
+        static bool done_[DGM_MAX_DEVICES] = {false};
+        if (p4_lds_attr(mlp_dw4_group_kernel<8, 1, 1024, 512, 128, 64>, CfgDwH::LDS, &done_[current_device_slot()]) != hipSuccess)
+            return mlp_fail("mlp: cannot raise the LDS limit of a plane-path kernel");
+        hipLaunchKernelGGL((mlp_dw4_group_kernel<8, 1, 1024, 512, 128, 64>), dim3(chunks_s, 2), dim3(512), CfgDwH::LDS, st, dg);
+    }
+    ReduceDwBatch rb;
+    memset(&rb, 0, sizeof(rb));
+    rb.emb_dim = nets[0].p->emb_dim;  // (the caller checked: the same for both networks)
+    int rb_blocks = 0, n_pending = 0;
+    auto add_job = [&](const dgm_mlp_params* p, int chunks, int db_rows, int Kp, int in_features, int dst_off, const float* partial,
+                       const float* partial_db, float* dWp, float* dbp) {
+        ReduceDwJob& jb = rb.job[n_pending++];
+        jb.chunks = chunks, jb.db_rows = db_rows, jb.Kp = Kp, jb.in_features = in_features, jb.nblocks = reduce_dw_blocks(Kp);
+        jb.emb_rows = EW, jb.k_valid = MLP_XE;
+        jb.dst_off = dst_off, jb.partial = partial, jb.partial_db = partial_db, jb.dW = dWp, jb.db = dbp;
+        if (jb.nblocks > rb_blocks) rb_blocks = jb.nblocks;
+    };
+    for (int l = 7; l >= 0; l--) {
+        if (l == 0 || l == sk) {  // the embedding's rows of the gradient, with the layer's bias gradient
+            for (int i = 0; i < 2; i++) {
+                const Ws& w = nets[i].w;
+                Dw4Args& d = dg.a[i];
+                d.ntiles = nt, d.tiles_per_chunk = tpc_s;
+                d.X = (const unsigned char*)w.emb, d.Xexp = w.Eexp, d.G = G[i], d.Gexp = Ge[i];
+                d.partial = l == sk ? w.partial_l[l] + (size_t)n_dw * MLP_W * MLP_W : w.partial_l[l];
+                d.chunk_stride = (size_t)EW * MLP_W, d.partial_db = w.partial_db_l[l];
+                add_job(nets[i].p, chunks_s, 8 * chunks_s, EW, layer_in(nets[i].p, l), 0, d.partial, d.partial_db, nets[i].dW[l], nets[i].db[l]);
+            }
+            static bool done_[DGM_MAX_DEVICES] = {false};
+            if (p4_lds_attr(mlp_dw4_group_kernel<2, 8, 256, 128, 1024, 512>, CfgDwE64::LDS, &done_[current_device_slot()]) != hipSuccess)
+                return mlp_fail("mlp: cannot raise the LDS limit of a plane-path kernel");
+            hipLaunchKernelGGL((mlp_dw4_group_kernel<2, 8, 256, 128, 1024, 512>), dim3(chunks_s, 2), dim3(512), CfgDwE64::LDS, st, dg);
+        }
+        if (l == 0) break;
+        for (int i = 0; i < 2; i++) {  // backward data G_{l-1} = (G_l W_l) masked, into the other buffer; the trunk rows of dW_l
+            const Ws& w = nets[i].w;
+            Gemm4Args& a = pg.ga[i];
+            a.A = G[i], a.Aexp = Ge[i], a.Bp = w.Wd3[l], a.b_inv = w.wsc_d[l], a.mask_in = w.mask[l - 1], a.C = Gn[i], a.Cexp = Gne[i];
+            Dw4Args& d = pg.da[i];
+            d.tiles_per_chunk = tpc_pair;
+            d.X = (const unsigned char*)w.Y[l - 1], d.Xexp = w.Yexp[l - 1], d.G = G[i], d.Gexp = Ge[i];
+            d.partial = w.partial_l[l], d.chunk_stride = (size_t)MLP_W * MLP_W;
+            d.partial_db = l == sk ? nullptr : w.partial_db_l[l];  // (the skip layer's bias gradient came with its embedding half)
+            if (l == sk)
+                add_job(nets[i].p, chunks_pair, 0, MLP_W, layer_in(nets[i].p, l), nets[i].p->emb_dim, d.partial, nullptr, nets[i].dW[l], nullptr);
+            else
+                add_job(nets[i].p, chunks_pair, 8 * chunks_pair, MLP_W, layer_in(nets[i].p, l), 0, d.partial, d.partial_db, nets[i].dW[l], nets[i].db[l]);
+        }
+        dgm::prof_begin(DGM_STAGE_MLP_BWD_PAIR, st, 2);  // (counts as the two layer passes it carries)
+        {
+            static bool done_[DGM_MAX_DEVICES] = {false};
+            constexpr int LDS_PAIR = CfgBwdC::LDS > CfgDw::LDS ? CfgBwdC::LDS : CfgDw::LDS;
+            if (p4_lds_attr(mlp_bwd_pair_group_kernel<true>, LDS_PAIR, &done_[current_device_slot()]) != hipSuccess)
+                return mlp_fail("mlp: cannot raise the LDS limit of mlp_bwd_pair_group_kernel");
+            hipLaunchKernelGGL(mlp_bwd_pair_group_kernel<true>, dim3(4 * n_wg), dim3(512), LDS_PAIR, st, pg, n_wg, cpw, n_dw);
+        }
+        dgm::prof_end(DGM_STAGE_MLP_BWD_PAIR, st);
+        for (int i = 0; i < 2; i++) {
+            unsigned char* t = G[i];
+            G[i] = Gn[i], Gn[i] = t;
+            int* te = Ge[i];
+            Ge[i] = Gne[i], Gne[i] = te;
+        }
+    }
+    rb.n_jobs = n_pending;  // 18: what two backward_planes() passes queue, job for job
+    for (int i = 0; i < 2; i++) {
+        ReduceDwBatch::Heads& h = rb.heads[i];
+        h.chunks = chunks_s, h.bchunks = nt, h.nout = nets[i].p->n_out;
+        h.partial_W = nets[i].w.partial_h, h.partial_b = nets[i].w.partial_hb, h.dW = nets[i].dWh, h.db = nets[i].dbh;
+    }
+    hipLaunchKernelGGL(mlp_reduce_dw_all_kernel, dim3(rb_blocks, rb.n_jobs + 2), dim3(256), 0, st, rb);
+    {   // the time columns of dW_0 / dW_skip: db (x) t_emb; and dL/dt_emb
+        FoldGradGroupArgs fg;
+        int tmax = 0;
+        bool any_dt = false;
+        for (int i = 0; i < 2; i++) {
+            const dgm_mlp_params* p = nets[i].p;
+            FoldGradArgs& f = fg.f[i];
+            f.dW[0] = nets[i].dW[0], f.db[0] = nets[i].db[0], f.W[0] = p->W[0], f.in_features[0] = layer_in(p, 0);
+            f.dW[1] = nets[i].dW[sk], f.db[1] = nets[i].db[sk], f.W[1] = p->W[sk], f.in_features[1] = layer_in(p, sk);
+            f.temb = nets[i].w.temb_row, f.T = p->t_dim, f.dtemb = nets[i].dtemb;
+            if (p->t_dim > tmax) tmax = p->t_dim;
+            any_dt = any_dt || f.dtemb != nullptr;
+        }
+        hipLaunchKernelGGL(mlp_fold_grad_group_kernel, dim3(any_dt ? 3 : 2, tmax, 2), dim3(256), 0, st, fg);
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return mlp_fail(hipGetErrorString(e));
     return 0;
@@ -1399,15 +1570,22 @@ int dgm_mlp_describe_workspace(int N, size_t* offs, int capacity) {
 
 int dgm_mlp_forward(const dgm_mlp_params* p, int N, const float* x, const float* temb, int temb_stride, char* workspace,
                     float* out, void* stream) {
+    return dgm_mlp_forward_add(p, N, x, nullptr, 0, temb, temb_stride, workspace, out, stream);
+}
+
+int dgm_mlp_forward_add(const dgm_mlp_params* p, int N, const float* x, const float* x_add, int x_add_stride, const float* temb,
+                        int temb_stride, char* workspace, float* out, void* stream) {
     if (check_params(p)) return 1;
     if (N <= 0) return 0;
     if (!x || !temb || !workspace || !out) return mlp_fail("mlp_forward: NULL pointer");
+    if (x_add && (g_gemm_mode < 3 || x_add_stride < 3))
+        return mlp_fail("mlp_forward_add: the addend exists in the plane arithmetic only (f16x3p), rows of at least 3 floats");
     hipStream_t st = (hipStream_t)stream;
     Ws w = carve(workspace, N);
     const int mode = g_gemm_mode;
     const bool fold = (mode == 3 || mode == 5) && temb_stride == 0;
     remember_ws_mode(workspace, mode + (fold ? 16 : 0));
-    if (mode >= 3) return forward_planes(p, N, x, temb, temb_stride, w, out, st, fold, fold && mode == 5);
+    if (mode >= 3) return forward_planes(p, N, x, temb, temb_stride, w, out, st, fold, fold && mode == 5, x_add, x_add_stride);
     // ---- native fp32 MFMA
     for (int l = 0; l < 8; l++) {
         const int Kp = layer_kp(p, l);
@@ -1513,6 +1691,35 @@ int dgm_mlp_backward_dx(const dgm_mlp_params* p, int N, const float* dOut, int t
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return mlp_fail(hipGetErrorString(e));
     return 0;
+}
+
+int dgm_mlp_backward_group(const dgm_mlp_backward_job* a, const dgm_mlp_backward_job* b, int N, int temb_stride, void* stream) {
+    if (!a || !b) return mlp_fail("mlp_backward_group: NULL job");
+    const dgm_mlp_backward_job* jobs[2] = {a, b};
+    if (check_params(a->params) || check_params(b->params)) return 1;
+    if (N <= 0) return 0;
+    for (const dgm_mlp_backward_job* j : jobs)
+        if (!j->dOut || !j->workspace || !j->dWh || !j->dbh) return mlp_fail("mlp_backward_group: NULL pointer");
+    if (a->workspace == b->workspace) return mlp_fail("mlp_backward_group: the two networks need workspaces of their own");
+    const int mode = g_gemm_mode;
+    const int fa = recall_ws_mode(a->workspace), fb = recall_ws_mode(b->workspace);
+    const int n_wg = p4_group_split(N);
+    const bool grouped = n_wg > 0 && mode == 3 && temb_stride == 0 && fa == (3 | 16) && fb == (3 | 16) &&
+                         a->params->emb_dim == b->params->emb_dim;
+    if (!grouped) {  // two ordinary passes back to back: what the caller would have run (and every check of theirs)
+        for (const dgm_mlp_backward_job* j : jobs)
+            if (dgm_mlp_backward(j->params, N, j->dOut, temb_stride, j->workspace, j->dW, j->db, j->dWh, j->dbh, j->dtemb, stream)) return 1;
+        return 0;
+    }
+    GroupNet nets[2];
+    for (int i = 0; i < 2; i++) {
+        const dgm_mlp_backward_job* j = jobs[i];
+        for (int l = 0; l < 8; l++)
+            if (!j->dW[l] || !j->db[l]) return mlp_fail("mlp_backward_group: NULL gradient pointer");
+        nets[i].p = j->params, nets[i].dOut = j->dOut, nets[i].w = carve(j->workspace, N);
+        nets[i].dW = j->dW, nets[i].db = j->db, nets[i].dWh = j->dWh, nets[i].dbh = j->dbh, nets[i].dtemb = j->dtemb;
+    }
+    return backward_planes_group(nets, N, n_wg, (hipStream_t)stream);
 }
 
 int dgm_timenet_forward(const float* t, int n_freq, const float* W1, const float* b1, int hidden, const float* W2,

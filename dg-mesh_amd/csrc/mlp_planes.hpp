@@ -192,11 +192,12 @@ struct AbsMaxBatch {
 // preparation, which needs them -- followed by ntiles workgroups (one 32-row tile each).
 __device__ __forceinline__ void embed4_tile(const int N, const int tile, const float* __restrict__ x, const float* __restrict__ temb,
                                             const int temb_stride, const int T, unsigned char* __restrict__ Ep, int* __restrict__ Eexp,
-                                            const int EW, float (*se)[96 + 1], float* smax);
+                                            const int EW, float (*se)[96 + 1], float* smax, const float* __restrict__ xadd = nullptr,
+                                            const int xadd_stride = 0);
 __global__ void __launch_bounds__(256)
 mlp_embed4_kernel(int N, int ntiles, const float* __restrict__ x, const float* __restrict__ temb, int temb_stride, int T,
                   unsigned char* __restrict__ Ep, int* __restrict__ Eexp, const AbsMaxBatch am, unsigned* __restrict__ matmax,
-                  const int EW) {
+                  const int EW, const float* __restrict__ xadd, const int xadd_stride) {
     __shared__ float se[32][96 + 1];
     __shared__ float smax[4];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -226,11 +227,14 @@ mlp_embed4_kernel(int N, int ntiles, const float* __restrict__ x, const float* _
         if (tid == 0) matmax[job * AS + part] = __float_as_uint(fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3])));
         return;
     }
-    embed4_tile(N, (int)blockIdx.x - n_am, x, temb, temb_stride, T, Ep, Eexp, EW, se, smax);
+    embed4_tile(N, (int)blockIdx.x - n_am, x, temb, temb_stride, T, Ep, Eexp, EW, se, smax, xadd, xadd_stride);
 }
 __device__ __forceinline__ void embed4_tile(const int N, const int tile, const float* __restrict__ x, const float* __restrict__ temb,
                                             const int temb_stride, const int T, unsigned char* __restrict__ Ep, int* __restrict__ Eexp,
-                                            const int EW, float (*se)[96 + 1], float* smax) {
+                                            const int EW, float (*se)[96 + 1], float* smax, const float* __restrict__ xadd,
+                                            const int xadd_stride) {
+    // xadd (may be NULL): the position is x[r] + xadd[r][0..2], one fp32 sum (the inverse deformation network reads the deformed
+    // means, x + d_xyz, straight from the deformation network's output rows)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int r0 = tile * 32;
     float mx = 0.f;
@@ -241,7 +245,11 @@ __device__ __forceinline__ void embed4_tile(const int N, const int tile, const f
             const int sub = lane / 30, p = lane - 30 * sub, rl = 8 * wv + 2 * it + sub, r = r0 + rl;
             const int q = p / 3, a = p - 3 * q;
             float sn = 0.f, cs = 0.f;
-            if (r < N) sincosf(x[3 * r + a] * (float)(1 << q), &sn, &cs);
+            if (r < N) {
+                float xv = x[3 * r + a];
+                if (xadd != nullptr) xv += xadd[(size_t)r * xadd_stride + a];
+                sincosf(xv * (float)(1 << q), &sn, &cs);
+            }
             se[rl][3 + 6 * q + a] = sn;
             se[rl][6 + 6 * q + a] = cs;
         }
@@ -255,7 +263,10 @@ __device__ __forceinline__ void embed4_tile(const int N, const int tile, const f
         int c;
         if (j < 3) {
             c = j;
-            if (r < N) v = x[3 * r + j];
+            if (r < N) {
+                v = x[3 * r + j];
+                if (xadd != nullptr) v += xadd[(size_t)r * xadd_stride + j];
+            }
         } else {
             const int t = j - 3;
             c = 63 + t;
@@ -423,22 +434,21 @@ mlp_prep4c_kernel(const Prep4cBatch b) {
 // one 32-row tile of the embedding each.  (Two launches: 13.1 + 10.2 us.)
 __global__ void __launch_bounds__(256)
 mlp_embed4c_kernel(const int N, const float* __restrict__ x, unsigned char* __restrict__ Ep, int* __restrict__ Eexp, const int EW,
-                   const Prep4cBatch b, const int n_prep) {
+                   const Prep4cBatch b, const int n_prep, const float* __restrict__ xadd, const int xadd_stride) {
     if ((int)blockIdx.x < n_prep) {  // (workgroup-uniform)
         prep4c_block(b, (int)blockIdx.x % (256 / P4C_COLS), (int)blockIdx.x / (256 / P4C_COLS));
         return;
     }
     __shared__ float se[32][96 + 1];
     __shared__ float smax[4];
-    embed4_tile(N, (int)blockIdx.x - n_prep, x, nullptr, 0, 0, Ep, Eexp, EW, se, smax);
+    embed4_tile(N, (int)blockIdx.x - n_prep, x, nullptr, 0, 0, Ep, Eexp, EW, se, smax, xadd, xadd_stride);
 }
 
 // ---- dOut (N, n_out) fp32 -> planes [Np][2][32] + exponents, and the heads' bias-gradient partial sums --------------------
 // One wave per 32-row tile (lane = row, column half); columns >= n_out and rows >= N are zero, which is what makes every
 // gradient tensor's padded rows exactly zero.  partial_b[tile][16] = column sums of the tile (the heads' bias gradient).
-__global__ void __launch_bounds__(256)
-mlp_dout4_kernel(int N, int ntiles, int NC, const float* __restrict__ dOut, unsigned char* __restrict__ Dp, int* __restrict__ Dexp,
-                 float* __restrict__ partial_b) {
+__device__ __forceinline__ void dout4_body(int N, int ntiles, int NC, const float* __restrict__ dOut, unsigned char* __restrict__ Dp,
+                                           int* __restrict__ Dexp, float* __restrict__ partial_b) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int tile = blockIdx.x * 4 + wv;
     if (tile >= ntiles) return;
@@ -475,6 +485,11 @@ mlp_dout4_kernel(int N, int ntiles, int NC, const float* __restrict__ dOut, unsi
         for (int dd = 16; dd >= 1; dd >>= 1) s += __shfl_xor(s, dd, 64);
         if (rl == 0) partial_b[(size_t)tile * 16 + 8 * hf + i] = s;
     }
+}
+__global__ void __launch_bounds__(256)
+mlp_dout4_kernel(int N, int ntiles, int NC, const float* __restrict__ dOut, unsigned char* __restrict__ Dp, int* __restrict__ Dexp,
+                 float* __restrict__ partial_b) {
+    dout4_body(N, ntiles, NC, dOut, Dp, Dexp, partial_b);
 }
 
 // ---- the layer GEMM on planes ----------------------------------------------------------------------------------------------
@@ -1081,8 +1096,12 @@ __device__ __forceinline__ void dw4_body(const Dw4Args& a, const int chunk, unsi
     if (nst <= 0) return;
 
     // E_ref = min over the chunk's tiles of ex + eg
+    // (every wave for itself, a lane per tile and a butterfly: ONE round trip to memory per 64 tiles -- a scalar loop over the
+    // chunk's tiles was a chain of dependent loads, several microseconds in front of every chunk; a minimum has no order)
     int eref = 0x7fffffff;
-    for (int t = t0; t < t1; t++) eref = min(eref, a.Xexp[t] + a.Gexp[t]);
+    for (int t = t0 + lane; t < t1; t += 64) eref = min(eref, a.Xexp[t] + a.Gexp[t]);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) eref = min(eref, __shfl_xor(eref, d, 64));
     eref = __builtin_amdgcn_readfirstlane(eref);
 
     // stager geometry
@@ -1289,6 +1308,76 @@ mlp_bwd_pair_kernel(const Gemm4Args ga, const Dw4Args da, const int n_dw, const 
     } else {
         gemm4_body<16, 1024, 512, 1, false, 8, COLSC>(ga, (int)blockIdx.x - n_dw, (int)gridDim.x - n_dw, p4_smem);
     }
+}
+
+// ---- the backward passes of TWO networks in shared launches ---------------------------------------------------------------------
+// The deformation network and its inverse run their backward passes over the same N rows and need nothing of each other.  One
+// launch serves both: every workgroup works for ONE network (a workgroup-uniform choice: the argument set is read from the
+// kernel arguments with scalar loads), so a layer-GEMM workgroup keeps its stationary weights for twice the tiles and a
+// weight-gradient workgroup runs `cpw` of the single-network pass's row chunks one after the other.  The chunks themselves -- which
+// tiles a partial tile sums, in which order -- are exactly those of mlp_bwd_pair_kernel, so every partial tile, and with it every
+// gradient, has the bits of the single-network pass.
+// Paired launch: network i owns workgroups [2 i n_wg, 2 (i + 1) n_wg): the first n_wg on the weight gradient (chunks w cpw ..
+// w cpw + cpw - 1), the next n_wg on the layer GEMM, "chunked" as in mlp_bwd_pair_kernel (GEMM workgroup w walks the tiles of
+// weight-gradient workgroup w).  n_wg is a multiple of 8, so workgroup ids w, n_wg + w of either network land on the same XCD.
+struct PairGroupArgs {
+    Gemm4Args ga[2];
+    Dw4Args da[2];
+};
+template <bool COLSC>
+__global__ void __launch_bounds__(512)
+mlp_bwd_pair_group_kernel(const PairGroupArgs s, const int n_wg, const int cpw, const int n_chunks) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char p4_smem[];
+    const int net = __builtin_amdgcn_readfirstlane((int)blockIdx.x >= 2 * n_wg ? 1 : 0);
+    const int w = (int)blockIdx.x - net * 2 * n_wg;
+    if (w < n_wg) {
+        const Dw4Args& da = s.da[net];  // (by reference: the fields stay scalar loads from the kernel arguments)
+        const int c1 = min(n_chunks, (w + 1) * cpw);
+#pragma unroll 1
+        for (int c = w * cpw; c < c1; c++) {
+            dw4_body<8, 8, 1024, 512, 1024, 512>(da, c, p4_smem);
+            __syncthreads();  // (the next chunk's first stage overwrites the LDS buffers)
+        }
+    } else {
+        const Gemm4Args& ga = s.ga[net];
+        const int span = s.da[net].tiles_per_chunk * cpw;
+        const int first = (w - n_wg) * span;
+        const int cnt = min(span, ga.ntiles - first);
+        gemm4_body<16, 1024, 512, 1, false, 8, COLSC>(ga, first, 1, p4_smem, cnt > 0 ? cnt : 0);
+    }
+}
+// The stand-alone launches of a backward pass for both networks: blockIdx.y = network.
+struct Dw4GroupArgs {
+    Dw4Args a[2];
+};
+template <int MT, int NT, int XROWB, int XPLANEB, int GROWB, int GPLANEB>
+__global__ void __launch_bounds__(512)
+mlp_dw4_group_kernel(const Dw4GroupArgs s) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char p4_smem[];
+    const Dw4Args a = s.a[__builtin_amdgcn_readfirstlane((int)blockIdx.y)];
+    dw4_body<MT, NT, XROWB, XPLANEB, GROWB, GPLANEB>(a, (int)blockIdx.x, p4_smem);
+}
+struct Gemm4GroupArgs {
+    Gemm4Args a[2];
+};
+template <int KS, int ROWB, int PLANEB, int EPI, bool DUAL, int NCW, bool COLSC = false>
+__global__ void __launch_bounds__(512)
+mlp_gemm4_group_kernel(const Gemm4GroupArgs s) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char p4_smem[];
+    const Gemm4Args a = s.a[__builtin_amdgcn_readfirstlane((int)blockIdx.y)];
+    gemm4_body<KS, ROWB, PLANEB, EPI, DUAL, NCW, COLSC>(a, (int)blockIdx.x, (int)gridDim.x, p4_smem);
+}
+struct Dout4GroupArgs {
+    int NC[2];
+    const float* dOut[2];
+    unsigned char* Dp[2];
+    int* Dexp[2];
+    float* partial_b[2];
+};
+__global__ void __launch_bounds__(256)
+mlp_dout4_group_kernel(int N, int ntiles, const Dout4GroupArgs s) {
+    const int i = blockIdx.y;
+    dout4_body(N, ntiles, s.NC[i], s.dOut[i], s.Dp[i], s.Dexp[i], s.partial_b[i]);
 }
 
 // ---- gradient w.r.t. the positions -------------------------------------------------------------------------------------------

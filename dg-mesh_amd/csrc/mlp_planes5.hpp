@@ -502,8 +502,21 @@ struct FoldGradArgs {
     float* dtemb;  // may be NULL (then the grid is (2, T))
     int T;
 };
+__device__ __forceinline__ void fold_grad_body(const FoldGradArgs& f);
 __global__ void __launch_bounds__(256)
 mlp_fold_grad_kernel(const FoldGradArgs f) {
+    fold_grad_body(f);
+}
+struct FoldGradGroupArgs {  // two networks in one launch (grid (3 or 2, T, 2)); a network without dtemb leaves its blockIdx.x = 2 idle
+    FoldGradArgs f[2];
+};
+__global__ void __launch_bounds__(256)
+mlp_fold_grad_group_kernel(const FoldGradGroupArgs s) {
+    const FoldGradArgs& f = s.f[blockIdx.z];
+    if ((int)blockIdx.y >= f.T || (blockIdx.x == 2 && f.dtemb == nullptr)) return;  // (workgroup-uniform)
+    fold_grad_body(f);
+}
+__device__ __forceinline__ void fold_grad_body(const FoldGradArgs& f) {
     __shared__ float red[4];
     const int k = blockIdx.x, t = blockIdx.y, j = threadIdx.x;
     if (k < 2) {  // (workgroup-uniform)

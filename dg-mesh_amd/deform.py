@@ -290,6 +290,28 @@ class _ModelWrapper:
         self.net.load_state_dict(torch.load(os.path.join(root, f"iteration_{iteration}/{self.model_name}.pth")))
 
 
+def step_raw_pair(model, model_back, xyz, time_emb, time_emb_back):
+    """(raw, raw_back): model.step_raw(xyz, time_emb) and model_back.step_raw(xyz + raw[:, :3], time_emb_back) -- the inverse
+    network on the deformed means, taken as constants (R/train.py:208-216) -- as ONE autograd node, so that the two backward
+    passes run in shared launches (mlp_hip._MLPPairFunction).  None when the pair does not qualify: both networks plain
+    DeformNetwork heads on the "hip" trunk, device positions without a gradient, one time value per call."""
+    net, net_back = model.net, model_back.net
+    for n in (net, net_back):
+        if not isinstance(n, DeformNetwork) or n.is_6dof or n.trunk_impl != "hip":
+            return None
+    if not xyz.is_cuda or xyz.requires_grad:
+        return None
+    for t in (time_emb, time_emb_back):
+        if not (t.dim() == 2 and t.shape[0] > 1 and t.stride(0) == 0):  # (what _time_rows() broadcasts)
+            return None
+    from . import mlp_hip
+    if not mlp_hip.pair_supported(xyz, True, True):
+        return None
+    t_a, _ = net._time_rows(time_emb)
+    t_b, _ = net_back._time_rows(time_emb_back)
+    return mlp_hip.network_pair_forward(net, net.head_modules(), net_back, net_back.head_modules(), xyz, t_a, t_b)
+
+
 class DeformModel(_ModelWrapper):
     def __init__(self, is_blender=False, is_6dof=False, device="cuda", trunk_impl=None):
         super().__init__(DeformNetwork(is_blender=is_blender, is_6dof=is_6dof, trunk_impl=trunk_impl).to(device), 5, "deform")

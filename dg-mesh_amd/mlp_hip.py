@@ -1,4 +1,5 @@
-"""autograd.Function over the fused MLP entry points of libdgmesh_hip.so (dgm_mlp_forward / dgm_mlp_backward)."""
+"""autograd.Function over the fused MLP entry points of libdgmesh_hip.so (dgm_mlp_forward / dgm_mlp_backward, and
+dgm_mlp_backward_group for a network and its inverse in one node)."""
 import ctypes
 
 import torch
@@ -118,6 +119,80 @@ class _MLPFunction(torch.autograd.Function):
         return (dX, dtemb if need_t else None, None, None, *dWs, *dbs, *dW, *db)
 
 
+def _unpack(tensors, n_heads):
+    hw, hb, wb = tensors[:n_heads], tensors[n_heads:2 * n_heads], tensors[2 * n_heads:]
+    n_out = sum(w.shape[0] for w in hw)
+    Wh, bh = _stacked(hw, (n_out, hw[0].shape[1])), _stacked(hb, (n_out,))
+    return Wh, bh, [w.contiguous() for w in wb[:8]], [v.contiguous() for v in wb[8:]], [w.shape[0] for w in hw]
+
+
+class _MLPPairFunction(torch.autograd.Function):
+    """A network and its inverse as ONE autograd node (deform / deform_back of a train step, R/train.py:156-216): forward runs
+    network A on x, then network B on x + out_A[:, :3] -- the deformed means, the same fp32 sum the glue kernel writes as
+    means3D, taken as a constant like `means3D.detach()` -- and returns both raw head outputs.  Backward receives both dOut and
+    makes one dgm_mlp_backward_group call: every launch of the pass serves both networks.
+    inputs: x (N, 3, no gradient), the two broadcast time rows (1, T), the head counts, then per network what _MLPFunction takes:
+    n head weights, n head biases, W0..W7, b0..b7."""
+
+    @staticmethod
+    def forward(ctx, x, t_a, t_b, nh_a, nh_b, *tensors):
+        L = _lib.lib()
+        n_a = 2 * nh_a + 16
+        nets = [_unpack(tensors[:n_a], nh_a), _unpack(tensors[n_a:], nh_b)]
+        x = x.contiguous()
+        N = x.shape[0]
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        st = _lib.stream_ptr()
+        outs, wss, saved = [], [], []
+        with _lib.device_guard(x.device):
+            for i, ((Wh, bh, W, b, _), t) in enumerate(zip(nets, (t_a.contiguous(), t_b.contiguous()))):
+                ws = torch.empty(L.dgm_mlp_workspace_bytes(N), dtype=torch.uint8, device=x.device)
+                out = torch.empty((N, Wh.shape[0]), dtype=torch.float32, device=x.device)
+                p = _params(None, W, b, Wh, bh, t.shape[1])
+                if i == 0:
+                    _lib.check(L.dgm_mlp_forward(ctypes.byref(p), N, vp(x), vp(t), 0, vp(ws), vp(out), st))
+                else:  # the sum is formed where the embedding reads the positions: no launch, no (N, 3) tensor
+                    _lib.check(L.dgm_mlp_forward_add(ctypes.byref(p), N, vp(x), vp(outs[0]), outs[0].shape[1], vp(t), 0, vp(ws),
+                                                     vp(out), st))
+                outs.append(out)
+                wss.append(ws)
+                saved += [ws, Wh, bh, *W, *b]
+        ctx.save_for_backward(*saved)
+        ctx.meta = (N, (t_a.shape[1], t_b.shape[1]), (t_a.requires_grad, t_b.requires_grad), (nets[0][4], nets[1][4]))
+        return outs[0], outs[1]
+
+    @staticmethod
+    def backward(ctx, dOut_a, dOut_b):
+        L = _lib.lib()
+        N, Ts, need_t, head_rows = ctx.meta
+        saved = ctx.saved_tensors
+        dev = saved[0].device
+        jobs, keep, grads, dtembs = [], [], [], []
+        for i, dOut in enumerate((dOut_a, dOut_b)):
+            ws, Wh, bh, *wb = saved[19 * i:19 * (i + 1)]
+            W, b = wb[:8], wb[8:]
+            if dOut is None:
+                dOut = torch.zeros((N, Wh.shape[0]), dtype=torch.float32, device=dev)
+            dOut = dOut.contiguous()
+            dW = [torch.empty_like(w) for w in W]
+            db = [torch.empty_like(v) for v in b]
+            dWh, dbh = torch.empty_like(Wh), torch.empty_like(bh)
+            dtemb = torch.empty((1, Ts[i]), dtype=torch.float32, device=dev)
+            p = _params(None, W, b, Wh, bh, Ts[i])
+            j = _lib.MlpBackwardJob()
+            j.params, j.dOut, j.workspace = ctypes.pointer(p), dOut.data_ptr(), ws.data_ptr()
+            for l in range(8):
+                j.dW[l], j.db[l] = dW[l].data_ptr(), db[l].data_ptr()
+            j.dWh, j.dbh, j.dtemb = dWh.data_ptr(), dbh.data_ptr(), dtemb.data_ptr()
+            jobs.append(j)
+            keep.append((p, dOut))
+            dtembs.append(dtemb if need_t[i] else None)
+            grads += [*torch.split(dWh, head_rows[i], 0), *torch.split(dbh, head_rows[i], 0), *dW, *db]
+        with _lib.device_guard(dev):
+            _lib.check(L.dgm_mlp_backward_group(ctypes.byref(jobs[0]), ctypes.byref(jobs[1]), N, 0, _lib.stream_ptr()))
+        return (None, dtembs[0], dtembs[1], None, None, *grads)
+
+
 class _TimeNetFunction(torch.autograd.Function):
     """t (one device float) -> timenet(PE(t)) as a (1, n_out) row; gradients for the four timenet tensors only."""
 
@@ -198,3 +273,19 @@ def network_forward(net, heads, x, t_emb, bcast):
     W = [l.weight for l in net.linear]
     b = [l.bias for l in net.linear]
     return _MLPFunction.apply(x, t_emb, bcast, len(heads), *[m.weight for m in heads], *[m.bias for m in heads], *W, *b)
+
+
+def pair_supported(x, bcast_a, bcast_b):
+    """The pair node's conditions on the call (the caller has checked the networks): device tensors, positions without a
+    gradient, one time value per call on both networks, the plane arithmetic (dgm_mlp_forward_add)."""
+    return (x.is_cuda and not x.requires_grad and bcast_a and bcast_b and _lib.lib().dgm_mlp_set_gemm(-1) in (3, 4, 5))
+
+
+def network_pair_forward(net_a, heads_a, net_b, heads_b, x, t_emb_a, t_emb_b):
+    """(out_a, out_b) = (net_a(x), net_b(x + out_a[:, :3])) as one autograd node, see _MLPPairFunction."""
+    check_supported(net_a, heads_a, t_emb_a)
+    check_supported(net_b, heads_b, t_emb_b)
+    flat = []
+    for net, heads in ((net_a, heads_a), (net_b, heads_b)):
+        flat += [m.weight for m in heads] + [m.bias for m in heads] + [l.weight for l in net.linear] + [l.bias for l in net.linear]
+    return _MLPPairFunction.apply(x, t_emb_a, t_emb_b, len(heads_a), len(heads_b), *flat)

@@ -242,8 +242,12 @@ class Trainer:
     def __init__(self, gaussians, deform, deform_back, cameras, opt=None, pipe=None, background=None,
                  is_blender=True, is_6dof=False, rank=0, world=1, seed=0, render_fn=None, fused_adam=None,
                  process_group=None, fused_loss=True, fused_glue=None, track_stats=True, densify=False,
-                 cameras_extent=1.0, prune_threshold=0.005, white_background=True, overlap=False, mesh=None):
+                 cameras_extent=1.0, prune_threshold=0.005, white_background=True, overlap=False, mesh=None,
+                 group_mlp_backward=None):
         self.g, self.deform, self.deform_back = gaussians, deform, deform_back
+        # deform and deform_back as one autograd node whose backward runs both networks in shared launches (deform.step_raw_pair);
+        # default from DGM_MLP_GROUP (on), 0 = two nodes, two backward passes
+        self.group_mlp_backward = (os.environ.get("DGM_MLP_GROUP", "1") != "0") if group_mlp_backward is None else bool(group_mlp_backward)
         self.mesh = mesh
         self.cameras = cameras
         self.opt = opt or S.OptimizationParams()
@@ -496,7 +500,13 @@ class Trainer:
             N = g.get_xyz.shape[0]
             time_input = self.time_input(cam, N, iteration)   # fid + this iteration's first noise sample (R/train.py:158-166)
             t_back = self.time_input(cam, N, iteration)       # ... and its second one, for the backward networks (:208-216)
-            if self.fused_glue:  # raw (N, 13) head output straight into the fused glue kernels (glue.py)
+            back = None
+            if self.fused_glue and self.group_mlp_backward:  # both networks in one autograd node: one grouped backward pass
+                from .deform import step_raw_pair
+                pair = step_raw_pair(self.deform, self.deform_back, g.get_xyz.detach(), time_input, t_back)
+                if pair is not None:
+                    delta, back = pair
+            if self.fused_glue and delta is None:  # raw (N, 13) head output straight into the fused glue kernels (glue.py)
                 delta = self.deform.step_raw(g.get_xyz.detach(), time_input)
             if delta is None:
                 d_xyz, d_rotation, d_scaling = self.deform.step(g.get_xyz.detach(), time_input)[:3]
@@ -504,7 +514,13 @@ class Trainer:
         if delta is not None:
             from .glue import cycle_loss
             lean = {"lean": True} if self.render_fn is S.render else {}
-            if self.world > 1 and self._early is not None:
+            if back is not None:
+                # The pair node ran deform_back on get_xyz + delta[:, :3], the same fp32 sum the glue kernel forms as means3D.
+                # Its backward needs both dOut, so the rasterizer's backward -- after which the Gaussian gradients are final and
+                # their early all-reduce starts (data parallel) -- precedes both networks' backward passes.
+                pkg = self.render_fn(cam, g, self.pipe, self.bg, None, None, None, self.is_6dof, delta=delta, **lean)
+                losses["cycle_loss"] = cycle_loss(delta, back)
+            elif self.world > 1 and self._early is not None:
                 # Data parallel with the early Gaussian-bucket all-reduce: build the cycle branch BEFORE the render branch.
                 # Autograd runs later-built branches first, so the rasterizer's backward -- after which the Gaussian
                 # gradients are final and their all-reduce starts -- then precedes BOTH MLP backward passes instead of only

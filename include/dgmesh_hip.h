@@ -282,6 +282,12 @@ int dgm_mlp_describe_workspace(int N, size_t* offs, int capacity);
 int dgm_mlp_forward(const dgm_mlp_params* p, int N, const float* x, const float* temb, int temb_stride,
                     char* workspace, float* out, void* stream);
 
+/* The same with the positions formed on the fly: row r of the input is x[r] + x_add[r][0..2] (one fp32 sum; x_add has rows of
+ * x_add_stride >= 3 floats) -- the inverse deformation network on the deformed means x + d_xyz, read straight from the deformation
+ * network's output rows.  x_add may be NULL (= dgm_mlp_forward); plane arithmetic only, otherwise an error is returned. */
+int dgm_mlp_forward_add(const dgm_mlp_params* p, int N, const float* x, const float* x_add, int x_add_stride, const float* temb,
+                        int temb_stride, char* workspace, float* out, void* stream);
+
 /* Given dOut (N, n_out): dW[l] / db[l] in the layout of W[l] / b[l], dWh, dbh, and dtemb
  * ((t_dim) summed over rows when temb_stride == 0, else (N, t_dim)); dtemb may be NULL. */
 int dgm_mlp_backward(const dgm_mlp_params* p, int N, const float* dOut, int temb_stride, char* workspace,
@@ -294,6 +300,27 @@ int dgm_mlp_backward(const dgm_mlp_params* p, int N, const float* dOut, int temb
 int dgm_mlp_backward_dx(const dgm_mlp_params* p, int N, const float* dOut, int temb_stride, char* workspace,
                         float* const* dW, float* const* db, float* dWh, float* dbh, float* dtemb, const float* x, float* dX,
                         void* stream);
+
+/* The backward passes of TWO networks over the same N rows in shared launches: the deformation network and its inverse
+ * (dgmesh/train.py:156-216: deform and deform_back), whose backward passes need nothing of each other once both dOut exist.
+ * One job per network: what dgm_mlp_backward takes (dtemb may be NULL).  Every launch of the pass then serves both networks
+ * (eleven launches fewer), a layer-GEMM workgroup keeps one network's weights for twice the tiles, and ONE reduction launch sums
+ * both networks' partial tiles.  The weight gradients keep the row chunks and the summation order of dgm_mlp_backward: the
+ * gradients are bit-identical to two dgm_mlp_backward calls.  Grouping needs the default arithmetic (f16x3p) with a broadcast time row
+ * (temb_stride == 0) on both workspaces, the same emb_dim, and a batch large enough for the paired launches (N >= 32 768 on
+ * 256 CUs; DGM_MLP_PAIR=0 turns them off); otherwise the call runs two ordinary passes back to back, a then b, and is
+ * bit-identical to them. */
+typedef struct {
+    const dgm_mlp_params* params;
+    const float* dOut; /* (N, n_out) */
+    char* workspace;   /* of this network's forward pass */
+    float* dW[8];
+    float* db[8];
+    float* dWh;
+    float* dbh;
+    float* dtemb;
+} dgm_mlp_backward_job;
+int dgm_mlp_backward_group(const dgm_mlp_backward_job* a, const dgm_mlp_backward_job* b, int N, int temb_stride, void* stream);
 
 /* The time branch of the is_blender networks for ONE row (t is identical for every Gaussian of an iteration,
  * dgmesh/train.py:158): out (n_out) = W2 relu(W1 PE(t) + b1) + b2 with PE(t) = [t, sin(2^k t), cos(2^k t), k < n_freq]
