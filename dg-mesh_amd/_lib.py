@@ -134,6 +134,15 @@ SYMBOLS = {
     "dgm_emd_parts": (_i, [_i, _i]),
     "dgm_emd_scratch_floats": (_c.c_size_t, [_i, _i, _i]),
     "dgm_emd_approx": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_mesh_clean_tile": (_i, []),
+    "dgm_mesh_cc_scratch_bytes": (_c.c_size_t, [_i, _i]),
+    "dgm_mesh_cc_label": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_mesh_cc_stats": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_mesh_cc_select_scratch_bytes": (_c.c_size_t, []),
+    "dgm_mesh_cc_select": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
+    "dgm_mesh_compact_scratch_bytes": (_c.c_size_t, [_i, _i]),
+    "dgm_mesh_compact_count": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_mesh_compact_emit": (_i, [_i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dgm_png_unfilter": (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
     "dgm_image_ingest": (_i, [_i, _i, _i, _i, _vp, _c.POINTER(_f), _vp, _vp, _vp]),
     "dgm_png_expand": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp]),

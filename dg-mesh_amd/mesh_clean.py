@@ -1,0 +1,203 @@
+"""Cleaning an extracted mesh on the device: connected components, per-component statistics, selection and order-preserving
+compaction -- verts_on_largest_mesh of the reference (R/nvdiffrast_utils/dpsr_utils.py:345-368, igl on the host; R/ = dgmesh/) and
+its pymeshlab meshing_remove_connected_component_by_* calls (R/scene/gaussian_model.py:633-650), as kernels of csrc/mesh_clean.hip
+(DESIGN.md section 4.13).  igl, trimesh and pymeshlab are neither vendored nor dependencies.
+
+Definitions (this project's; include/dgmesh_hip.h states them for the C ABI):
+  * a face is valid iff its three indices are in [0, V) and pairwise different; two vertices are connected when a valid face uses
+    both -- connectivity through shared VERTICES, which is igl's adjacency_matrix + connected_components, not trimesh's shared-edge
+    split; a vertex no valid face uses is a component of its own;
+  * a component's label is its smallest vertex index;
+  * the criteria combine by AND; invalid faces are always dropped, and so is every vertex no surviving face uses;
+  * surviving vertices and faces keep their order.
+Everything is integers, comparisons and copies: the results are bit-reproducible.  fp32 vertices, int32 faces, CUDA/HIP tensors only
+-- no CPU fallback.  Host synchronisations: 8 bytes in connected_components (the count of out-of-range faces, which raises), 8 bytes
+in clean_mesh (the output sizes)."""
+import ctypes
+from dataclasses import dataclass
+
+import torch
+
+from . import _lib
+
+
+@dataclass(frozen=True)
+class CleanSpec:
+    """The criteria of clean_mesh.  largest: keep only the component with the most valid faces (ties: the smaller label);
+    min_faces: drop components with fewer valid faces; min_diameter_frac: drop components whose bounding-box diagonal is below this
+    fraction of the whole mesh's (measured against the whole mesh also when `largest` is set)."""
+    largest: bool = False
+    min_faces: int = 0
+    min_diameter_frac: float = 0.0
+
+    def any(self):
+        return bool(self.largest) or self.min_faces > 0 or self.min_diameter_frac > 0.0
+
+    def describe(self):
+        return f"largest_component {int(bool(self.largest))} min_component_faces {int(self.min_faces)} min_component_diameter {float(self.min_diameter_frac):g}"
+
+
+def as_spec(clean):
+    """None, a CleanSpec or a dict of its fields -> CleanSpec or None ("do nothing")."""
+    if clean is None or isinstance(clean, CleanSpec):
+        return clean
+    if isinstance(clean, dict):
+        return CleanSpec(**clean)
+    raise TypeError(f"mesh_clean: clean must be None, a CleanSpec or a dict of its fields, got {type(clean).__name__}")
+
+
+def _vp(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else ctypes.c_void_p(0)
+
+
+def _scratch(nbytes, dev):
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+
+
+def tile():
+    """The integers per workgroup of the compaction's scans (dgm_mesh_clean_tile)."""
+    return int(_lib.lib().dgm_mesh_clean_tile())
+
+
+def _faces(name, faces):
+    if not torch.is_tensor(faces) or not faces.is_cuda:
+        raise RuntimeError(f"mesh_clean.{name} needs CUDA/HIP tensors (dg-mesh_amd has no CPU path)")
+    if faces.dtype != torch.int32:
+        raise RuntimeError(f"mesh_clean.{name}: faces must be int32, got {faces.dtype}")
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"mesh_clean.{name}: faces must be (F, 3), got {tuple(faces.shape)}")
+    return faces.detach().contiguous()
+
+
+def _verts(name, verts, dev=None):
+    if not torch.is_tensor(verts) or not verts.is_cuda:
+        raise RuntimeError(f"mesh_clean.{name} needs CUDA/HIP tensors (dg-mesh_amd has no CPU path)")
+    if verts.dtype != torch.float32:
+        raise RuntimeError(f"mesh_clean.{name}: verts must be float32, got {verts.dtype}")
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError(f"mesh_clean.{name}: verts must be (V, 3), got {tuple(verts.shape)}")
+    if dev is not None and verts.device != dev:
+        raise ValueError(f"mesh_clean.{name}: verts on {verts.device}, faces on {dev}")
+    return verts.detach().contiguous()
+
+
+def connected_components(faces, num_verts):
+    """labels (num_verts,) int32: the smallest vertex index of each vertex's component.  Faces with a repeated index connect nothing;
+    a face with an index outside [0, num_verts) raises ValueError naming their count (the kernel range-checks before it indexes)."""
+    faces = _faces("connected_components", faces)
+    V, F = int(num_verts), int(faces.shape[0])
+    if V < 0:
+        raise ValueError(f"mesh_clean.connected_components: num_verts must be >= 0, got {num_verts}")
+    L = _lib.lib()
+    dev = faces.device
+    labels = torch.empty(V, dtype=torch.int32, device=dev)
+    info = torch.empty(2, dtype=torch.int32, device=dev)
+    scratch = _scratch(L.dgm_mesh_cc_scratch_bytes(V, F), dev)
+    with _lib.device_guard(dev):
+        _lib.check(L.dgm_mesh_cc_label(V, F, _vp(faces), _vp(scratch), _vp(labels), _vp(info), _lib.stream_ptr()))
+        bad = int(info[0])  # host synchronisation
+    if bad:
+        raise ValueError(f"mesh_clean.connected_components: {bad} of {F} faces have an index outside [0, {V})")
+    return labels
+
+
+def _stats(verts, faces, labels):
+    L = _lib.lib()
+    V, F, dev = int(verts.shape[0]), int(faces.shape[0]), faces.device
+    comp_faces = torch.empty(V, dtype=torch.int32, device=dev)
+    comp_verts = torch.empty(V, dtype=torch.int32, device=dev)
+    comp_bbox = torch.empty((V, 6), dtype=torch.float32, device=dev)
+    with _lib.device_guard(dev):
+        _lib.check(L.dgm_mesh_cc_stats(V, F, _vp(verts), _vp(faces), _vp(labels), _vp(comp_faces), _vp(comp_verts), _vp(comp_bbox),
+                                       _lib.stream_ptr()))
+    return comp_faces, comp_verts, comp_bbox
+
+
+def _labels(name, labels, V, dev):
+    if not torch.is_tensor(labels) or not labels.is_cuda:
+        raise RuntimeError(f"mesh_clean.{name} needs CUDA/HIP tensors (dg-mesh_amd has no CPU path)")
+    if labels.dtype != torch.int32 or tuple(labels.shape) != (V,) or labels.device != dev:
+        raise ValueError(f"mesh_clean.{name}: labels must be ({V},) int32 on {dev}")
+    return labels.contiguous()
+
+
+def component_table(verts, faces, labels=None):
+    """One row per component, ordered by label: {"label", "faces" (valid faces), "verts": (C,) int32, "bbox_min", "bbox_max":
+    (C, 3) float32}, device tensors.  labels: connected_components' (computed when None)."""
+    faces = _faces("component_table", faces)
+    verts = _verts("component_table", verts, faces.device)
+    V = int(verts.shape[0])
+    labels = connected_components(faces, V) if labels is None else _labels("component_table", labels, V, faces.device)
+    comp_faces, comp_verts, comp_bbox = _stats(verts, faces, labels)
+    roots = torch.nonzero(comp_verts > 0).flatten()
+    return {"label": roots.to(torch.int32), "faces": comp_faces[roots], "verts": comp_verts[roots],
+            "bbox_min": comp_bbox[roots, :3].contiguous(), "bbox_max": comp_bbox[roots, 3:].contiguous()}
+
+
+def keep_mask(verts, faces, labels=None, *, largest=False, min_faces=0, min_diameter_frac=0.0):
+    """(F,) uint8, 1 for the faces clean_mesh keeps."""
+    faces = _faces("keep_mask", faces)
+    verts = _verts("keep_mask", verts, faces.device)
+    if int(min_faces) < 0 or not float(min_diameter_frac) >= 0.0:
+        raise ValueError(f"mesh_clean: need min_faces >= 0 and min_diameter_frac >= 0, got {min_faces} and {min_diameter_frac}")
+    L = _lib.lib()
+    V, F, dev = int(verts.shape[0]), int(faces.shape[0]), faces.device
+    labels = connected_components(faces, V) if labels is None else _labels("keep_mask", labels, V, dev)
+    comp_faces, comp_verts, comp_bbox = _stats(verts, faces, labels)
+    keep = torch.empty(F, dtype=torch.uint8, device=dev)
+    scratch = _scratch(L.dgm_mesh_cc_select_scratch_bytes(), dev)
+    with _lib.device_guard(dev):
+        _lib.check(L.dgm_mesh_cc_select(V, F, _vp(faces), _vp(labels), _vp(comp_faces), _vp(comp_verts), _vp(comp_bbox),
+                                        int(bool(largest)), int(min_faces), float(min_diameter_frac), _vp(scratch), _vp(keep),
+                                        _lib.stream_ptr()))
+    return keep
+
+
+def compact(verts, faces, keep):
+    """The faces with keep != 0 and the vertices they use, in their old order: (verts', faces' re-indexed, vert_index, face_index),
+    the last two int32, the old index of each survivor.  One 8-byte read-back (the sizes)."""
+    faces = _faces("compact", faces)
+    verts = _verts("compact", verts, faces.device)
+    V, F, dev = int(verts.shape[0]), int(faces.shape[0]), faces.device
+    if not torch.is_tensor(keep) or keep.device != dev or keep.dtype not in (torch.uint8, torch.bool) or tuple(keep.shape) != (F,):
+        raise ValueError(f"mesh_clean.compact: keep must be ({F},) uint8 or bool on {dev}")
+    keep = keep.contiguous().view(torch.uint8)
+    L = _lib.lib()
+    scratch = _scratch(L.dgm_mesh_compact_scratch_bytes(V, F), dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    with _lib.device_guard(dev):
+        _lib.check(L.dgm_mesh_compact_count(V, F, _vp(faces), _vp(keep), _vp(scratch), _vp(counts), _lib.stream_ptr()))
+        Vn, Fn = counts.tolist()  # the one host synchronisation: the output sizes
+        verts_out = torch.empty((Vn, 3), dtype=torch.float32, device=dev)
+        faces_out = torch.empty((Fn, 3), dtype=torch.int32, device=dev)
+        vert_index = torch.empty(Vn, dtype=torch.int32, device=dev)
+        face_index = torch.empty(Fn, dtype=torch.int32, device=dev)
+        _lib.check(L.dgm_mesh_compact_emit(V, F, _vp(verts), _vp(faces), _vp(scratch), Vn, Fn, _vp(verts_out), _vp(faces_out),
+                                           _vp(vert_index), _vp(face_index), _lib.stream_ptr()))
+    return verts_out, faces_out, vert_index, face_index
+
+
+def clean_mesh(verts, faces, *, largest=False, min_faces=0, min_diameter_frac=0.0, return_index=False):
+    """The mesh without the components that fail a criterion (CleanSpec), without invalid faces and without unused vertices:
+    (verts', faces') or, with return_index, (verts', faces', vert_index, face_index) -- the old index of every survivor, with which
+    a caller gathers per-vertex attributes.  An empty result has (0, 3) tensors."""
+    keep = keep_mask(verts, faces, largest=largest, min_faces=min_faces, min_diameter_frac=min_diameter_frac)
+    out = compact(verts, faces, keep)
+    return out if return_index else out[:2]
+
+
+def verts_on_largest_mesh(verts, faces):
+    """The reference's name (R/nvdiffrast_utils/dpsr_utils.py:345): clean_mesh(largest=True), device tensors."""
+    return clean_mesh(verts, faces, largest=True)
+
+
+def apply(clean, verts, faces, *attributes):
+    """clean (as_spec) applied to a mesh and per-vertex attribute tensors: (verts', faces', *attributes gathered with vert_index);
+    the inputs themselves when clean is None."""
+    spec = as_spec(clean)
+    if spec is None:
+        return (verts, faces) + attributes
+    v, f, vi, _ = clean_mesh(verts, faces, largest=spec.largest, min_faces=spec.min_faces, min_diameter_frac=spec.min_diameter_frac,
+                             return_index=True)
+    vi = vi.long()
+    return (v, f) + tuple(None if a is None else a[vi] for a in attributes)

@@ -190,13 +190,17 @@ def eval_distance(gt_verts, gt_faces, eval_verts, eval_faces, rotate=None, cam_o
     return chamfer, emd_cd(gs[None], es[None])["EMD"]
 
 
-def evaluation(gt_mesh_path, eval_mesh_path, eval_model_type, emd_sample=8192, seed=0):
+def evaluation(gt_mesh_path, eval_mesh_path, eval_model_type, emd_sample=8192, seed=0, clean=None):
     """evaluation of R/mesh_evaluation.py:98-178: the sorted *.obj of gt_mesh_path against the sorted *.ply of eval_mesh_path,
     -> (avg_cd, cd_list, avg_emd, emd_list) as Python floats.  camera_origin is read from ../transforms_train.json of the ground
     truth when that file exists and has the key.  Runs on the current device; the samples come from one generator seeded with `seed`.  The results stay
     on the device until one read-back after the last mesh.  ValueError: an unknown eval_model_type, no meshes, or folders of
-    different sizes (raised before the device is touched)."""
+    different sizes (raised before the device is touched).  clean: None, or a mesh_clean.CleanSpec (or a dict of its fields): each
+    PREDICTED mesh loses the components that fail it before it is scored (mesh_clean.clean_mesh, which reads the output sizes back
+    per mesh); a prediction of which nothing is left raises ValueError."""
+    from . import mesh_clean
     from .ply_io import read_mesh_ply
+    clean = mesh_clean.as_spec(clean)
     if eval_model_type not in ROTATIONS:
         raise ValueError(f"mesh_eval.evaluation: eval_model_type {eval_model_type!r} not supported (one of {sorted(ROTATIONS)})")
     gt_list = sorted(glob.glob(os.path.join(gt_mesh_path, "*.obj")))
@@ -218,7 +222,12 @@ def evaluation(gt_mesh_path, eval_mesh_path, eval_model_type, emd_sample=8192, s
         gv, gf = read_mesh_obj(gt_file)
         ev, ef = read_mesh_ply(eval_file)
         to = lambda a: torch.from_numpy(a).to(dev)
-        cd, emd = eval_distance(to(gv), to(gf), to(ev), to(ef), rotate=ROTATIONS[eval_model_type], cam_origin=cam_origin,
+        ev, ef = to(ev), to(ef)
+        if clean is not None:
+            ev, ef = mesh_clean.apply(clean, ev, ef)
+            if ev.shape[0] == 0:
+                raise ValueError(f"mesh_eval.evaluation: nothing of {eval_file} is left after cleaning ({clean.describe()})")
+        cd, emd = eval_distance(to(gv), to(gf), ev, ef, rotate=ROTATIONS[eval_model_type], cam_origin=cam_origin,
                                 emd_sample=emd_sample, generator=generator)
         table[i, 0], table[i, 1] = cd, emd
     host = table.cpu().numpy()  # the one read-back
@@ -226,14 +235,33 @@ def evaluation(gt_mesh_path, eval_mesh_path, eval_model_type, emd_sample=8192, s
     return float(np.mean(cd_list)), cd_list, float(np.mean(emd_list)), emd_list
 
 
-def main(argv=None):
-    """The command line of R/mesh_evaluation.py:181-248; returns the path of the eval_results.txt it wrote."""
+def build_parser():
     ap = argparse.ArgumentParser(prog="python -m dgmesh_amd.mesh_eval", description=__doc__.split("\n\n")[0])
     ap.add_argument("--path", required=True, help="scene folder holding gt/ and the method's folder")
     ap.add_argument("--eval_type", required=True, choices=sorted(ROTATIONS))
     ap.add_argument("--emd_sample", type=int, default=8192)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--largest_component", action="store_true", help="score only the largest component of each predicted mesh")
+    ap.add_argument("--min_component_faces", type=int, default=0, metavar="N", help="drop predicted components with fewer faces")
+    ap.add_argument("--min_component_diameter", type=float, default=0.0, metavar="FRAC",
+                    help="drop predicted components whose box diagonal is below FRAC of the whole mesh's")
+    return ap
+
+
+def clean_from_args(args):
+    """The mesh_clean.CleanSpec of the three component flags, or None when none is set."""
+    from .mesh_clean import CleanSpec
+    spec = CleanSpec(largest=args.largest_component, min_faces=args.min_component_faces, min_diameter_frac=args.min_component_diameter)
+    if spec.min_faces < 0 or not spec.min_diameter_frac >= 0.0:
+        raise ValueError("--min_component_faces and --min_component_diameter must be >= 0")
+    return spec if spec.any() else None
+
+
+def main(argv=None):
+    """The command line of R/mesh_evaluation.py:181-248; returns the path of the eval_results.txt it wrote."""
+    ap = build_parser()
     args = ap.parse_args(argv)
+    clean = clean_from_args(args)
     folder = FOLDERS.get(args.eval_type)
     if folder is None:
         ap.error(f"--eval_type {args.eval_type} has no folder in the reference's command line: call evaluation() with the two folders")
@@ -245,7 +273,8 @@ def main(argv=None):
     item_name = os.path.basename(os.path.dirname(os.path.abspath(gt_path)))
     log_folder = os.path.join(pred_root, "results", item_name + time.strftime("_%Y-%m-%d_%H-%M-%S", time.localtime()))
     print(f"GT path: {gt_path} \nPred path: {pred_path} \nLog folder: {log_folder}")
-    avg_cd, cd_list, avg_emd, emd_list = evaluation(gt_path, pred_path, args.eval_type, emd_sample=args.emd_sample, seed=args.seed)
+    avg_cd, cd_list, avg_emd, emd_list = evaluation(gt_path, pred_path, args.eval_type, emd_sample=args.emd_sample, seed=args.seed,
+                                                    clean=clean)
     for i, (cd, emd) in enumerate(zip(cd_list, emd_list)):
         print(f"Item {i}: CD {cd:.10f}, EMD {emd:.4f}")
     print(f"Average Chamfer distance: {avg_cd:.4f}")
@@ -257,6 +286,8 @@ def main(argv=None):
         fh.write(f"Pred source: {pred_path}\n")
         fh.write(f"Average Chamfer distance: {avg_cd:.10f}\n")
         fh.write(f"Average EMD: {avg_emd:.4f}\n")
+        if clean is not None:
+            fh.write(f"Predicted meshes cleaned: {clean.describe()}\n")
     return out
 
 

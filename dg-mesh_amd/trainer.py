@@ -223,10 +223,11 @@ class MeshPhase:
         return verts * g.gaussian_scale + g.gaussian_center, faces
 
     @torch.no_grad()
-    def extract_mesh(self, g, deform=None, deform_normal=None, t=None):
+    def extract_mesh(self, g, deform=None, deform_normal=None, t=None, clean=None):
         """export_mesh (R/scene/gaussian_model_dpsr_dynamic_anchor.py:831-856): world-space (verts, faces) of the surface at time t.
         deform / deform_normal: DeformModel-like objects with .step(xyz, t) (the first output is used), or None for the canonical
-        Gaussians; t: a scalar time (float or tensor).  Write the result with ply_io.write_mesh_ply."""
+        Gaussians; t: a scalar time (float or tensor).  clean: None, or a mesh_clean.CleanSpec (or a dict of its fields): the
+        components that fail it are removed (mesh_clean.clean_mesh).  Write the result with ply_io.write_mesh_ply."""
         if self.dpsr is None:
             raise RuntimeError("MeshPhase.extract_mesh needs the DPSR module")
         xyz = g.get_xyz
@@ -235,7 +236,11 @@ class MeshPhase:
         d_normal = deform_normal.step(xyz.detach(), tt) if deform_normal is not None else None
         if isinstance(d_normal, (tuple, list)):
             d_normal = d_normal[0]
-        return self.surface(g, self.psr(g, d_xyz, d_normal))
+        verts, faces = self.surface(g, self.psr(g, d_xyz, d_normal))
+        if clean is None:
+            return verts, faces
+        from . import mesh_clean
+        return mesh_clean.apply(clean, verts, faces)
 
 
 class Trainer:

@@ -60,7 +60,7 @@ extern "C" {
  *      (rendering a checkpoint), dgm_emd_* (mesh evaluation), dgm_png_unfilter / dgm_image_ingest (reading a dataset),
  *      dgm_image_composite_bytes / dgm_resample (resizing a dataset's images), dgm_lpips* (LPIPS of the test views),
  *      dgm_png_expand / dgm_image_ingest_masked / dgm_resample_nearest (real captures: mask PNGs and masked frames); dgm_png_unfilter
- *      also takes channels = 1. */
+ *      also takes channels = 1; dgm_mesh_* (cleaning an extracted mesh). */
 #define DGM_ABI_VERSION 5
 
 /* Allocator callback: must return a device pointer to at least `bytes` bytes (128-byte aligned),
@@ -665,6 +665,44 @@ int dgm_emd_parts(int rows, int cols);
 size_t dgm_emd_scratch_floats(int b, int n, int m);
 int dgm_emd_approx(int b, int n, int m, const float* xyz1, const float* xyz2, float* scratch, float* cost, float* residual,
                    void* stream);
+
+/* ---- cleaning an extracted mesh: components, floaters, compaction (csrc/mesh_clean.hip) ---------------------------------------------
+ * Replaces verts_on_largest_mesh (dgmesh/nvdiffrast_utils/dpsr_utils.py:345-368, igl on the host) and pymeshlab's
+ * meshing_remove_connected_component_by_* calls (dgmesh/scene/gaussian_model.py:633-650).  verts (V, 3) fp32, faces (F, 3) int32;
+ * every buffer is device memory, nothing is allocated and nothing is read back; integers, comparisons and copies only, so every
+ * output is bit-reproducible.  A face is VALID iff its three indices are in [0, V) and pairwise different; two vertices are
+ * connected when a valid face uses both (through shared vertices, as igl's adjacency_matrix + connected_components).
+ *   dgm_mesh_clean_tile: the integers per workgroup of the scans (their fixed partition).
+ *   dgm_mesh_cc_label: labels[v] = the smallest vertex index of v's component (a vertex no valid face uses: v itself).  info[0] =
+ *       the faces with an index outside [0, V), info[1] = the faces with indices in range of which two are equal; neither kind
+ *       connects anything, and no index is used before it is range-checked.  scratch: dgm_mesh_cc_scratch_bytes(V, F) bytes (0
+ *       for a negative size), contents irrelevant.  Lock-free union-find by minimum: one hooking launch, one labelling launch.
+ *   dgm_mesh_cc_stats: indexed by root (= label): comp_faces (V) valid faces, comp_verts (V) vertices, comp_bbox (V, 6) = (min xyz,
+ *       max xyz); an index that is no root gets 0, 0 and (+inf, -inf).  Floats are ordered by their bits (-0 < +0; a NaN beyond
+ *       the infinity of its sign).  A label outside [0, V) is skipped.
+ *   dgm_mesh_cc_select: keep[f] (F bytes, 0 / 1) = f is valid, and, where largest != 0, its component is the one with the most valid
+ *       faces (ties: the smaller label); and, where min_faces > 0, comp_faces >= min_faces; and, where min_diameter_frac > 0,
+ *       d2(component) >= (frac * frac) * d2(mesh) with d2(box) = (dx dx + dy dy) + dz dz, d = max - min, all in fp32 without
+ *       contraction, the mesh's box being the min / max over the roots' boxes.  scratch: dgm_mesh_cc_select_scratch_bytes() bytes.
+ *   dgm_mesh_compact_count: counts[0] = V', the vertices used by a kept face; counts[1] = F', the kept faces (a kept face with an
+ *       index outside [0, V) counts as dropped).  The caller reads the two ints back to size the outputs.  scratch:
+ *       dgm_mesh_compact_scratch_bytes(V, F) bytes (0 for a negative size), handed on to the emit call unchanged.
+ *   dgm_mesh_compact_emit: the survivors in their old order: verts_out (V', 3), faces_out (F', 3) re-indexed, vert_index (V') and
+ *       face_index (F') = the old index of each.  Vn, Fn: the counts; nothing is written at or behind them.  NULL outputs are
+ *       allowed where a count is 0. */
+int dgm_mesh_clean_tile(void);
+size_t dgm_mesh_cc_scratch_bytes(int V, int F);
+int dgm_mesh_cc_label(int V, int F, const int* faces, char* scratch, int* labels, int* info, void* stream);
+int dgm_mesh_cc_stats(int V, int F, const float* verts, const int* faces, const int* labels, int* comp_faces, int* comp_verts,
+                      float* comp_bbox, void* stream);
+size_t dgm_mesh_cc_select_scratch_bytes(void);
+int dgm_mesh_cc_select(int V, int F, const int* faces, const int* labels, const int* comp_faces, const int* comp_verts,
+                       const float* comp_bbox, int largest, int min_faces, float min_diameter_frac, char* scratch, unsigned char* keep,
+                       void* stream);
+size_t dgm_mesh_compact_scratch_bytes(int V, int F);
+int dgm_mesh_compact_count(int V, int F, const int* faces, const unsigned char* keep, char* scratch, int* counts, void* stream);
+int dgm_mesh_compact_emit(int V, int F, const float* verts, const int* faces, char* scratch, int Vn, int Fn, float* verts_out,
+                          int* faces_out, int* vert_index, int* face_index, void* stream);
 
 /* ---- dataset ingest: PNG unfiltering and compositing over the background (csrc/ingest.hip) -------------------------------------------
  * Replaces PIL's decoder and the numpy compositing of readCamerasFromTransforms + PILtoTorch (dgmesh/scene/dataset_readers.py:288-302,
