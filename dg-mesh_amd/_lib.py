@@ -143,6 +143,10 @@ SYMBOLS = {
     "dgm_mesh_compact_scratch_bytes": (_c.c_size_t, [_i, _i]),
     "dgm_mesh_compact_count": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dgm_mesh_compact_emit": (_i, [_i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_surf_closest_scratch_bytes": (_c.c_size_t, [_i, _i]),
+    "dgm_surf_closest": (_i, [_i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_surf_interp": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp]),
+    "dgm_corr_palette": (_i, [_i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "dgm_png_unfilter": (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
     "dgm_image_ingest": (_i, [_i, _i, _i, _i, _vp, _c.POINTER(_f), _vp, _vp, _vp]),
     "dgm_png_expand": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp]),

@@ -60,7 +60,7 @@ extern "C" {
  *      (rendering a checkpoint), dgm_emd_* (mesh evaluation), dgm_png_unfilter / dgm_image_ingest (reading a dataset),
  *      dgm_image_composite_bytes / dgm_resample (resizing a dataset's images), dgm_lpips* (LPIPS of the test views),
  *      dgm_png_expand / dgm_image_ingest_masked / dgm_resample_nearest (real captures: mask PNGs and masked frames); dgm_png_unfilter
- *      also takes channels = 1; dgm_mesh_* (cleaning an extracted mesh). */
+ *      also takes channels = 1; dgm_mesh_* (cleaning an extracted mesh); dgm_surf_* / dgm_corr_palette (mesh correspondence). */
 #define DGM_ABI_VERSION 5
 
 /* Allocator callback: must return a device pointer to at least `bytes` bytes (128-byte aligned),
@@ -703,6 +703,28 @@ size_t dgm_mesh_compact_scratch_bytes(int V, int F);
 int dgm_mesh_compact_count(int V, int F, const int* faces, const unsigned char* keep, char* scratch, int* counts, void* stream);
 int dgm_mesh_compact_emit(int V, int F, const float* verts, const int* faces, char* scratch, int Vn, int Fn, float* verts_out,
                           int* faces_out, int* vert_index, int* face_index, void* stream);
+
+/* ---- closest point on a triangle mesh, interpolation, correspondence colours (csrc/surface.hip) -------------------------------------
+ * What carries a surface point from one frame's mesh onto another's (correspondence.py).  verts (V, 3) fp32, faces (F, 3) int32;
+ * every buffer is device memory, nothing is allocated and nothing is read back.
+ *   dgm_surf_closest: per query point (N, 3) the closest point of the mesh as face (N) int32, d2 (N) fp32 = its squared distance and
+ *       bary (N, 3) fp32 = ((1 - v) - w, v, w).  Per (point, face) pair Ericson's region test in fp32 without contraction, in the
+ *       order written out at the head of csrc/surface.hip; the answer is the lexicographic minimum of (d2, face index) over the
+ *       faces with d2 < max_d2 (strict), none: face = -1, d2 = +inf, bary = 0.  Never chosen: a face with an index outside [0, V),
+ *       one whose fp32 normal length is not positive and finite, a NaN d2.  Bit-reproducible.  Finite max_d2: a hashed grid over
+ *       the faces in scratch, dgm_surf_closest_scratch_bytes(N, F) bytes (0 for a negative size; unused for max_d2 = +inf, may
+ *       then be NULL); max_d2 = +inf: a tiled brute force.
+ *   dgm_surf_interp: out (N, C) = (attr[i0] b0 + attr[i1] b1) + attr[i2] b2 per channel, attr (V, C) fp32, (i0, i1, i2) the
+ *       corners of face[n], b = bary[n]; a row whose face is outside [0, F) or has an index outside [0, V) is `fill`.
+ *   dgm_corr_palette: out (N, 3) = the colour of position xyz (N, 3): u = clamp(((x - center) / scale) 0.5 + 0.5, 0, 1) per axis,
+ *       center (3) and scale (1) fp32 in DEVICE memory; mode 0: u; mode 1: u times 0.55 where
+ *       floor(u_x cells) + floor(u_y cells) + floor(u_z cells) is odd (1 <= cells <= 4096); a row with a NaN: (1, 0, 1). */
+size_t dgm_surf_closest_scratch_bytes(int N, int F);
+int dgm_surf_closest(int N, int V, int F, const float* points, const float* verts, const int* faces, float max_d2, char* scratch,
+                     int* face, float* d2, float* bary, void* stream);
+int dgm_surf_interp(int N, int V, int F, int C, const float* attr, const int* faces, const int* face, const float* bary, float fill,
+                    float* out, void* stream);
+int dgm_corr_palette(int N, const float* xyz, const float* center, const float* scale, int mode, int cells, float* out, void* stream);
 
 /* ---- dataset ingest: PNG unfiltering and compositing over the background (csrc/ingest.hip) -------------------------------------------
  * Replaces PIL's decoder and the numpy compositing of readCamerasFromTransforms + PILtoTorch (dgmesh/scene/dataset_readers.py:288-302,
