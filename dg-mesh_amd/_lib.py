@@ -143,6 +143,11 @@ SYMBOLS = {
     "dgm_mesh_compact_scratch_bytes": (_c.c_size_t, [_i, _i]),
     "dgm_mesh_compact_count": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dgm_mesh_compact_emit": (_i, [_i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_mesh_simplify_scratch_bytes": (_c.c_size_t, [_i, _i]),
+    "dgm_mesh_simplify_box": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_mesh_simplify_count": (_i, [_i, _i, _vp, _vp, _f, _f, _f, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_mesh_simplify_place": (_i, [_i, _i, _vp, _vp, _vp, _f, _f, _f, _i, _i, _i, _f, _c.c_double, _vp, _vp, _vp]),
+    "dgm_mesh_simplify_vert_map": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     "dgm_surf_closest_scratch_bytes": (_c.c_size_t, [_i, _i]),
     "dgm_surf_closest": (_i, [_i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
     "dgm_surf_interp": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp]),

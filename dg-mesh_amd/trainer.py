@@ -223,11 +223,13 @@ class MeshPhase:
         return verts * g.gaussian_scale + g.gaussian_center, faces
 
     @torch.no_grad()
-    def extract_mesh(self, g, deform=None, deform_normal=None, t=None, clean=None):
+    def extract_mesh(self, g, deform=None, deform_normal=None, t=None, clean=None, simplify=None):
         """export_mesh (R/scene/gaussian_model_dpsr_dynamic_anchor.py:831-856): world-space (verts, faces) of the surface at time t.
         deform / deform_normal: DeformModel-like objects with .step(xyz, t) (the first output is used), or None for the canonical
         Gaussians; t: a scalar time (float or tensor).  clean: None, or a mesh_clean.CleanSpec (or a dict of its fields): the
-        components that fail it are removed (mesh_clean.clean_mesh).  Write the result with ply_io.write_mesh_ply."""
+        components that fail it are removed (mesh_clean.clean_mesh).  simplify: None, or a mesh_simplify.SimplifySpec (or a dict of its
+        fields): the mesh is then decimated by quadric vertex clustering (mesh_simplify.simplify_mesh), after `clean`.  Write the
+        result with ply_io.write_mesh_ply."""
         if self.dpsr is None:
             raise RuntimeError("MeshPhase.extract_mesh needs the DPSR module")
         xyz = g.get_xyz
@@ -237,10 +239,13 @@ class MeshPhase:
         if isinstance(d_normal, (tuple, list)):
             d_normal = d_normal[0]
         verts, faces = self.surface(g, self.psr(g, d_xyz, d_normal))
-        if clean is None:
-            return verts, faces
-        from . import mesh_clean
-        return mesh_clean.apply(clean, verts, faces)
+        if clean is not None:
+            from . import mesh_clean
+            verts, faces = mesh_clean.apply(clean, verts, faces)
+        if simplify is not None:
+            from . import mesh_simplify
+            verts, faces = mesh_simplify.apply(simplify, verts, faces)
+        return verts, faces
 
 
 class Trainer:

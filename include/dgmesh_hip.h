@@ -704,6 +704,49 @@ int dgm_mesh_compact_count(int V, int F, const int* faces, const unsigned char* 
 int dgm_mesh_compact_emit(int V, int F, const float* verts, const int* faces, char* scratch, int Vn, int Fn, float* verts_out,
                           int* faces_out, int* vert_index, int* face_index, void* stream);
 
+/* ---- simplifying an extracted mesh: quadric vertex clustering (csrc/mesh_simplify.hip) ------------------------------------------------
+ * Uniform-grid vertex clustering with quadric-error placement (Lindstrom 2000); with a tiny cell it is pymeshlab's
+ * meshing_merge_close_vertices + meshing_remove_duplicate_faces + meshing_remove_null_faces (dgmesh/scene/gaussian_model.py:603-697).
+ * verts (V, 3) fp32, faces (F, 3) int32, cell size h > 0 fp32; every buffer is device memory, nothing is allocated and nothing is
+ * read back.  Definitions:
+ *   VALID face: indices in [0, V) (range-checked before any use) and pairwise different, all nine coordinates finite; every other
+ *       face is dropped.  A vertex is USED when a valid face uses it.
+ *   BOX: per axis the min o and the max hi over the used vertices, floats ordered by their bits (-0 < +0), no float arithmetic.
+ *   CELLS: n_k = max(1, ceil((hi_k - o_k) / h)), idx_k = min(n_k - 1, floor((x_k - o_k) / h)), fp32 with correctly rounded subtract
+ *       and divide, no contraction; n_k <= 2^20; key = (idx_z n_y + idx_y) n_x + idx_x, 64-bit.  The caller computes n from the box
+ *       it read back and passes o, n, h to the later calls.
+ *   CLUSTERS: the used vertices of one occupied cell; representative = the smallest old vertex index; new vertices are ordered by
+ *       representative.  vert_map (V) old -> new, -1 for a vertex no surviving face uses; vert_index new -> representative.
+ *   FACES: every valid face remapped; NULL when two new indices coincide, DUPLICATE when a face with a smaller old index has the
+ *       same unordered triple; both are dropped, survivors keep their order, face_index new -> old; a cluster left without a face is
+ *       dropped.  Winding is kept as remapped (clustering can flip a triangle; not repaired).  The triple is not packed into one
+ *       word: there is no limit on the number of clusters.
+ *   PLACEMENT (fp64 from the fp32 inputs, no contraction): per cluster with cell centre c = o + (idx + 0.5) h, over the valid faces S
+ *       with at least one corner in it, each once, in ascending old face index: n = (p1 - p0) x (p2 - p0), d = -n . (p0 - c),
+ *       g = (p0 + p1 + p2) / 3 - c; A = sum n n^T, b = sum n d, xh = (sum g) / |S|; mu = regularization tr(A); mu == 0: x = xh,
+ *       otherwise (A + mu I) x = mu xh - b (Cholesky); x clamped per component to [-h, h]; new vertex = fp32(c + x).
+ * Every output is bit-reproducible: the per-cluster sums run over an inverted index in ascending face order, no float is added by
+ * an atomic.  F <= 2^29.
+ *   dgm_mesh_simplify_box: marks valid faces and used vertices in scratch; box (6 floats, device) = (o, hi), (+inf, -inf) without a
+ *       valid face.  scratch: dgm_mesh_simplify_scratch_bytes(V, F) bytes (0 for a negative or unsupported size), handed on to the
+ *       later calls unchanged.
+ *   dgm_mesh_simplify_count (no placement): after _box; the cluster map, rep_faces (F, 3) = every face's corners replaced by their
+ *       representatives' OLD indices (-1 for an invalid face), keep (F bytes) = valid, not null, not duplicate, and through
+ *       dgm_mesh_compact_count on (rep_faces, keep) counts[0] = V', counts[1] = F'.  compact_scratch:
+ *       dgm_mesh_compact_scratch_bytes(V, F) bytes.  May be called again with another h on the same scratch.
+ *   dgm_mesh_simplify_place: after _count with the same grid; placed (V, 3) = the new position at every representative's row (other
+ *       rows: the old position).  dgm_mesh_compact_emit on (placed, rep_faces, compact_scratch) then gives verts', faces',
+ *       vert_index and face_index.
+ *   dgm_mesh_simplify_vert_map: after the emit; vert_map (V) from vert_index (Vn). */
+size_t dgm_mesh_simplify_scratch_bytes(int V, int F);
+int dgm_mesh_simplify_box(int V, int F, const float* verts, const int* faces, char* scratch, float* box, void* stream);
+int dgm_mesh_simplify_count(int V, int F, const float* verts, const int* faces, float ox, float oy, float oz, int nx, int ny, int nz,
+                            float h, char* scratch, char* compact_scratch, int* rep_faces, unsigned char* keep, int* counts,
+                            void* stream);
+int dgm_mesh_simplify_place(int V, int F, const float* verts, const int* faces, const int* rep_faces, float ox, float oy, float oz, int nx,
+                            int ny, int nz, float h, double regularization, char* scratch, float* placed, void* stream);
+int dgm_mesh_simplify_vert_map(int V, int F, int Vn, const int* vert_index, char* scratch, int* vert_map, void* stream);
+
 /* ---- closest point on a triangle mesh, interpolation, correspondence colours (csrc/surface.hip) -------------------------------------
  * What carries a surface point from one frame's mesh onto another's (correspondence.py).  verts (V, 3) fp32, faces (F, 3) int32;
  * every buffer is device memory, nothing is allocated and nothing is read back.
