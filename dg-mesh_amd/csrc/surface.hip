@@ -24,7 +24,8 @@
 //   * finite max_d2: a hashed uniform grid over the FACES.  A face is registered in every cell its box overlaps; the box is the
 //     face's AABB widened by 2^-19 of its largest |coordinate| S per axis: q is a rounded combination of the corners and may leave
 //     the exact AABB -- ab, ac, their products with v and w, the two sums and v + w <= 1 up to rounding add up to at most 16 * 2^-24 S,
-//     half the widening (v and w of a sliver whose |n|^2 drowns in the rounding of the products are not covered).  Cell edge c = max(1.001 sqrt(max_d2), 1.001 E, 2^-20 extent), E = the largest box edge of a
+//     half the widening (v and w of a sliver, whose |n|^2 drowns in the rounding of the products, stay within rounding of [0, 1] all
+//     the same: measured and asserted by tests/test_surface_host.py).  Cell edge c = max(1.001 sqrt(max_d2), 1.001 E, 2^-20 extent), E = the largest box edge of a
 //     candidate face, reduced on the device and read by the later kernels from device memory.  A box then spans at most two cells
 //     per axis: at most 8 references per face (the upper cell is clamped to lower + 1, so the bound holds by construction), and the
 //     scratch is known on the host.  Cell coordinates are taken in fp64 from fp32 values (anchor.hip); a face with fp32

@@ -139,6 +139,36 @@ def test_correspond_onto_another_tessellation(moving_torus):
     assert torch.equal(tight["position"][~torch.as_tensor(lost, device=DEV)], r["position"][~torch.as_tensor(lost, device=DEV)])
 
 
+class Identity:
+    """Both networks of a mesh that does not move: a zero offset."""
+
+    def step(self, x, t):
+        return (torch.zeros_like(x),)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("max_dist", [1.0 / 23, math.inf])
+def test_correspond_marching_cubes_sphere_onto_itself(max_dist):
+    """SR.mc_sphere(1e-6): a marching-cubes mesh whose isosurface grazes six lattice nodes -- 96 faces thinner than 1e-3, 72 thinner
+    than 1e-5, edges down to 8e-8.  Under the identity motion every vertex is found on its own mesh, within one voxel and without a
+    bound, at a distance of at most 8 eps S, and its barycentrics rebuild it within 8 eps S (the bound of
+    tests/test_surface_host.py::test_barycentrics_are_a_point_of_the_face: the roundings of v, w and (1 - v) - w, each eps S)."""
+    C = pkg("correspondence")
+    verts, faces = SR.mc_sphere(1e-6)
+    v, f, still = dev(verts), dev(faces), Identity()
+    r = C.correspond(v, T_A, v, f, T_B, still, still, max_dist=max_dist)
+    assert torch.equal(r["position_free"], v)
+    S = float(np.abs(verts).max())
+    dist = float(r["d2"].max().sqrt())
+    rebuilt = float((r["position"] - v).double().pow(2).sum(1).sqrt().max())
+    face, bary = r["face"].cpu().numpy(), r["bary"].cpu().numpy()
+    thin = (SR.thinness(verts, faces)[face[face >= 0]] < 1e-3).sum()
+    print(f"mc_sphere(1e-6) onto itself, max_dist {max_dist:.4f}: found {(face >= 0).sum()} of {len(verts)} ({thin} on a face thinner than "
+          f"1e-3), max distance {dist / (EPS * S):.2f} eps S, rebuilt within {rebuilt / (EPS * S):.2f} eps S (bounds 8)")
+    assert (face >= 0).all() and dist <= 8 * EPS * S and rebuilt <= 8 * EPS * S
+    assert bary.min() >= -4 * EPS and bary.max() <= 1 + 4 * EPS
+
+
 # ---- drivers --------------------------------------------------------------------------------------------------------------------------
 N_FRAMES, SIDE, K_TRACKS = 3, 176, 256
 

@@ -8,7 +8,35 @@ the largest |coordinate|, d the float64 distance): the rounding of a squared dis
 size S.  Measured with this file's restatement on exactly this seeded input (numpy on the CPU):
     |min d2 (fp32) - min d2 (fp64)| / E(d)                       2.33   (over all N x F pairs: 7.68)
     (fp64 d2 of the face fp32 chose - fp64 min d2) / E(d)        0.70
-The assertions allow twice the measured values; the slack is for numpy builds, the inputs are seeded."""
+The assertions allow twice the measured values; the slack is for numpy builds, the inputs are seeded.
+
+Thin faces.  A torus has none; a marching-cubes mesh has them wherever the isosurface grazes a lattice node, and there the rounding of
+the products that form va, vb, vc exceeds |n|^2, so v and w of the interior rule are not accurate.  The second half of this file
+holds the statement to what the kernel's candidate-set argument needs of it on such input, and measures
+its accuracy there.  Inputs (tests/_surface_ref.py, seeded; V / F; faces with thinness = height / longest edge below 1e-3 / 1e-5):
+    mc_sphere(delta), delta 1e-3, 1e-5, 1e-6       678 / 1352     0 / 0 (thinnest 1.64e-3: 48 below 2e-3), 96 / 0, 96 / 72; edges down to 8.4e-8
+    split_torus(h), h 1e-4, 1e-6, 1e-7             1200 / 2400    400 / 0, 400 / 400, 400 / 400
+    sliver_soup(500, 1e-2, h, S), h 1e-5, 3e-7,    1500 / 500     245 to 500 / 0 to 500; at h below the float32 spacing up to 48 faces
+      3e-8, S 1, 10                                               are collinear in float32 and refused
+    micro_triangles()                              624 / 208      |n|^2 normal for 12 faces, denormal for 63, zero for 133
+each with sliver_queries: 3 x 400 points on thin faces displaced by 0, 1e-6, 1e-4, 1200 near faces, every vertex, 16 far points.
+Measured with numpy on the CPU, over all 5.0e7 (query, candidate face) pairs:
+    q leaves the face's exact AABB by at most            1.92 * 2^-24 S_face   (the argument allows 16, the box is widened by 32)
+    v, w and (1 - v) - w of every pair lie in            [-1.0 eps, 1]         (asserted: [-4 eps, 1 + 4 eps])
+    pairs with a NaN or infinite dist2                   none, except 74 + 19 on 45 micro triangles with a denormal |n|^2, where
+                                                         den = 1 / ((va + vb) + vc) overflows; such a pair is never reported
+    a query on a mesh vertex gets dist2 == 0             every vertex of the six meshes; corner A of every candidate face
+    zero-displacement queries answered by a thin face    236, 141, 103 (mc_sphere), 42, 94, 127 (split_torus) of 400 (guard: 25)
+    |fp32 - fp64 distance| of the mesh-wide minimum, in eps S (S per query) and in max(eps S, height of the chosen face):
+        mc_sphere      847, 41, 7.2 eps S       0.32, 0.39, 0.39            (absolute: 4.0e-5, 1.9e-6, 3.4e-7)
+        split_torus    528, 5.3, 1.2 eps S      0.36, 0.46, 0.52            (absolute: 4.4e-5, 4.4e-7, 2.3e-7)
+        sliver_soup    71 to 73 160 eps S       4.3 to 73 160               (absolute: 4.2e-5 to 4.4e-3, up to 0.44 of the long edge)
+The unit that stays bounded on the meshes is the second: the fp32 distance is off by up to half the height of the sliver it picks
+(or eps S), because a neighbour across the sliver's long edges answers where the sliver's own v and w fail.  E(d) is the wrong unit
+there (up to 5e5 E(d) at d = 0), and K_MIN / K_CHOSEN are not asserted on these inputs.  An ISOLATED sliver has no such neighbour: below
+a thinness of about sqrt(eps) its closest point can be anywhere along it, in either unit without a bound; asserted there is what
+the range of the barycentrics gives -- the fp32 distance is never below the true one by more than 8 eps S (measured 1.25) and never
+above it by more than the longest edge of the closest face (measured 0.44 of it)."""
 import math
 
 import numpy as np
@@ -197,3 +225,152 @@ def test_c_abi_argument_errors_without_gpu():
     assert lib.dgm_corr_palette(4, None, None, None, 2, 8, None, None) != 0 and b"mode" in lib.dgm_last_error()
     assert lib.dgm_corr_palette(4, None, None, None, 1, 0, None, None) != 0 and b"cells" in lib.dgm_last_error()
     assert lib.dgm_corr_palette(4, None, None, None, 1, 8, None, None) != 0 and b"NULL" in lib.dgm_last_error()
+
+
+# ---- thin faces (module docstring, "Thin faces") --------------------------------------------------------------------------------------------
+SLIVER, MESHES, SOUPS = list(SR.SLIVER_CASES), list(SR.MESH_CASES), list(SR.SOUP_CASES)
+K_HEIGHT = 2 * 0.52  # |fp32 distance - fp64 distance| / max(eps S, height of the chosen face) on the six meshes: twice the measured
+FLT_MIN = np.float32(2.0 ** -126)
+_f64 = {}
+
+
+def sliver64(name):
+    """The float64 statement's answer on SR.sliver_case(name), once per process."""
+    if name not in _f64:
+        c = SR.sliver_case(name)
+        _f64[name] = SR.closest64(c["points"], c["verts"], c["faces"])
+    return _f64[name]
+
+
+def normal_len2(verts, faces):
+    """|n|^2 in fp32 by face_ok's operations."""
+    a, b, c = verts[faces[:, 0]], verts[faces[:, 1]], verts[faces[:, 2]]
+    with np.errstate(all="ignore"):
+        e1, e2 = b - a, c - a
+        nx, ny, nz = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2], e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+        return (nx * nx + ny * ny) + nz * nz
+
+
+def longest_edge(verts, f):
+    a, b, c = (verts[f[:, k]].astype(np.float64) for k in range(3))
+    return np.sqrt(np.maximum(np.maximum(((b - a) ** 2).sum(1), ((c - b) ** 2).sum(1)), ((a - c) ** 2).sum(1)))
+
+
+def test_sliver_inputs_are_the_stated_ones():
+    assert np.float32(1e-40) * np.float32(1) != 0, "this numpy flushes denormals: the statement would not be the kernel's"
+    for name in MESHES + SOUPS:
+        verts, faces = SR.SLIVER_CASES[name]()
+        assert verts.dtype == np.float32 and faces.dtype == np.int32
+        th = SR.thinness(verts, faces)
+        n = [(th < t).sum() for t in (1e-3, 1e-5)]
+        e = np.sqrt(((verts[faces] - verts[faces[:, [1, 2, 0]]]).astype(np.float64) ** 2).sum(-1))
+        print(f"{name}: V {len(verts)} F {len(faces)}, candidates {SR.face_ok(verts, faces).sum()}, thinness < 1e-3: {n[0]}, < 1e-5: {n[1]}, "
+              f"thinnest {th.min():.2e}, shortest edge {e.min():.1e}")
+        if name.startswith("mc"):
+            assert verts.shape == (678, 3) and faces.shape == (1352, 3)
+            edges = np.sort(np.concatenate([faces[:, [0, 1]], faces[:, [1, 2]], faces[:, [2, 0]]]), 1)
+            assert (np.unique(edges, axis=0, return_counts=True)[1] == 2).all()  # closed
+            assert n == {"mc_sphere_1e-3": [0, 0], "mc_sphere_1e-5": [96, 0], "mc_sphere_1e-6": [96, 72]}[name]
+            assert (th < SR.THIN.get(name, 1e-3)).sum() >= 48
+        elif name.startswith("split"):
+            assert verts.shape == (1200, 3) and faces.shape == (2400, 3) and n[0] == 400
+            assert np.array_equal(verts[:800], SR.torus(40, 20)[0])
+        else:
+            assert verts.shape == (1500, 3) and faces.shape == (500, 3) and n[0] >= 245
+    verts, faces = SR.micro_triangles()
+    n2 = normal_len2(verts, faces)
+    ok = SR.face_ok(verts, faces)
+    classes = [(n2 >= FLT_MIN).sum(), ((n2 > 0) & (n2 < FLT_MIN)).sum(), (n2 == 0).sum()]
+    print(f"micro: V {len(verts)} F {len(faces)}, |n|^2 normal {classes[0]}, denormal {classes[1]}, zero {classes[2]}; candidates {ok.sum()}")
+    assert faces.shape == (208, 3) and np.abs(verts).max() <= 1e-3 and min(classes) >= 10
+    assert np.array_equal(ok, n2 > 0)  # (sqrt of a positive denormal is positive: the rule accepts every denormal |n|^2)
+    for name in SLIVER:
+        assert len(SR.sliver_case(name)["points"]) == 2400 + len(SR.sliver_case(name)["verts"]) + SR.N_FAR
+
+
+@pytest.mark.parametrize("name", SLIVER)
+def test_sliver_structure(name):
+    """What the candidate-set argument of DESIGN.md section 4.14 needs of the pair arithmetic, on thin faces:
+      * bary within [-4 eps, 1 + 4 eps];
+      * over every (query, candidate face) pair that can be reported (finite dist2), q leaves the face's exact AABB by at most
+        16 * 2^-24 S_face, the constant of the argument (the boxes are widened by 32);
+      * no candidate pair with a NaN dist2.  Not so on the micro triangles: where (va + vb) + vc, which is |n|^2 up to rounding, falls
+        below 2^-128, den = 1 / that overflows, v and w are inf or 0 * inf, dist2 is inf or NaN and the face cannot be reported for
+        that query.  Asserted there: only faces with a denormal |n|^2 do that;
+      * a query equal to a mesh vertex gets dist2 == 0 exactly and a chosen face with a corner of those bits.  By the arithmetic that
+        holds for corner A of a candidate face (rule 1: v = w = 0, q = a).  For corner B (rule 2) q = a + fl(b - a), which is b only
+        where that difference and sum are exact: fl(b - a) is off by at most 2 eps S per axis and the sum rounds by eps S, 3 sqrt(3)
+        eps S in all; likewise C by rule 4 -- unless rule 3 takes it first: at p = c, vc is |n|^2 up to rounding, on a sliver of
+        either sign, and the answer is then the foot of c on ab, the face's height over ab away.  On the six meshes every vertex
+        is at dist2 == 0 (asserted); of an isolated triangle corner A is, and B and C lie within 6 eps S, C's height more."""
+    c = SR.sliver_case(name)
+    verts, faces, points, (f32, d32, b32), chk = c["verts"], c["faces"], c["points"], c["ref"], c["check"]
+    V = len(verts)
+    ok = SR.face_ok(verts, faces)
+    n2 = normal_len2(verts, faces)
+    vq = slice(2400, 2400 + V)
+    at_a, at_any = np.zeros(V, bool), np.zeros(V, bool)
+    at_a[faces[ok, 0]], at_any[faces[ok].ravel()] = True, True
+    zero = d32[vq] == 0
+    corner = (verts[faces[np.maximum(f32[vq], 0)]] == points[vq][:, None, :]).all(2).any(1) & (f32[vq] >= 0)
+    S = float(np.abs(verts).max())
+    a, b, cc = (verts[faces[:, k]].astype(np.float64) for k in range(3))
+    over_ab = np.sqrt((np.cross(b - a, cc - a) ** 2).sum(1)) / np.maximum(np.sqrt(((b - a) ** 2).sum(1)), 1e-300)
+    allow = np.zeros(V)
+    np.maximum.at(allow, faces[ok, 2], over_ab[ok])
+    far = float(((np.sqrt(d32[vq].astype(np.float64)) - allow)[at_any]).max())
+    print(f"{name}: bary in [{b32.min() / EPS:.2f} eps, 1 + {(b32.max() - 1) / EPS:.2f} eps], over all pairs in [{chk.bary_min / EPS:.2f} eps, "
+          f"1 + {(chk.bary_max - 1) / EPS:.2f} eps] (bound 4); q leaves the AABB by "
+          f"{chk.excursion:.3f} 2^-24 S_face (bound 16) over {chk.pairs} pairs; NaN dist2 {chk.nan_pairs}, inf {chk.inf_pairs}, on "
+          f"{len(chk.bad_faces)} faces; vertices at dist2 == 0: {zero.sum()} of {V} ({at_any.sum()} on a candidate, {at_a.sum()} as its "
+          f"corner A), the farthest of a candidate at its height as corner C + {far / (EPS * S):.2f} eps S (bound 6)")
+    assert (f32 >= 0).all() and ok[f32].all()
+    assert b32.min() >= -4 * EPS and b32.max() <= 1 + 4 * EPS
+    assert chk.bary_min >= -4 * EPS and chk.bary_max <= 1 + 4 * EPS  # (of every pair, not only of the chosen ones)
+    assert chk.excursion <= 16
+    bad = np.array(sorted(chk.bad_faces), np.int64)
+    if name == "micro":
+        assert (n2[bad] < FLT_MIN).all()
+    else:
+        assert chk.nan_pairs == 0 and chk.inf_pairs == 0
+    assert zero[at_a].all() and corner[at_a].all() and far <= 6 * EPS * S
+    if name in MESHES:
+        assert zero.all() and corner.all()
+
+
+@pytest.mark.parametrize("name", MESHES)
+def test_sliver_queries_reach_thin_faces(name):
+    """The guard: of the 400 queries on thin faces without displacement at least 25 get a thin face as their answer -- the tests of
+    this input cannot pass by never choosing one.  (A seed that gives fewer is replaced; the 25 stay.)"""
+    c = SR.sliver_case(name)
+    th = SR.thinness(c["verts"], c["faces"])
+    thin = SR.THIN.get(name, 1e-3)
+    n = int((th[c["ref"][0][:SR.N_ON]] < thin).sum())
+    print(f"{name}: {n} of {SR.N_ON} chosen faces have thinness < {thin:g} (at least 25)")
+    assert n >= 25
+
+
+@pytest.mark.parametrize("name", SLIVER)
+def test_sliver_accuracy_against_fp64(name):
+    """|fp32 distance - fp64 distance| of the mesh-wide minimum, in units of (i) eps S and (ii) max(eps S, height of the face fp32
+    chose).  (ii) stays bounded on the six meshes and is asserted there at twice the measured 0.52 (module docstring); (i) does not.
+    On isolated slivers neither does, and what is asserted is what the arithmetic gives: bary is within rounding of [0, 1], so q is a
+    point of the face and the fp32 distance no smaller than the true one up to 8 eps S, and no larger than it by more than the longest
+    edge of the closest face.  The micro triangles are printed only: float64 accepts all 208 faces, fp32 75 of them."""
+    c = SR.sliver_case(name)
+    verts, faces, points, (f32, d32, _) = c["verts"], c["faces"], c["points"], c["ref"]
+    f64, d64, _ = sliver64(name)
+    S = np.maximum(np.abs(verts).max(), np.abs(points).max(1)).astype(np.float64)  # (per query: the far group would set it for all)
+    diff = np.sqrt(d32.astype(np.float64)) - np.sqrt(d64)
+    E = EPS * S * (np.sqrt(d64) + EPS * S)
+    height = SR.thinness(verts, faces)[f32] * longest_edge(verts, faces[f32])
+    r_s, r_h = np.abs(diff) / (EPS * S), np.abs(diff) / np.maximum(EPS * S, height)
+    edge = longest_edge(verts, faces[f64])
+    print(f"{name}: |fp32 - fp64 distance| max {np.abs(diff).max():.2e} = {r_s.max():.2f} eps S = {r_h.max():.2f} max(eps S, height) "
+          f"(bound {K_HEIGHT} on the meshes); fp32 - fp64 in [{(diff / (EPS * S)).min():.2f} eps S, {(diff / edge).max():.3f} longest edges]; "
+          f"|d2 (fp32) - d2 (fp64)| max {(np.abs(d32 - d64) / E).max():.1f} E(d); argmin differs for {(f32 != f64).sum()} of {len(points)}")
+    if name in MESHES:
+        assert r_h.max() <= K_HEIGHT
+    elif name in SOUPS:  # (over the queries whose float64 face is a candidate in fp32 too)
+        both = SR.face_ok(verts, faces)[f64]
+        assert (diff / (EPS * S)).min() >= -8 and ((diff - edge) / (EPS * S))[both].max() <= 8

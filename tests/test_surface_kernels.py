@@ -176,6 +176,10 @@ def test_face_permutation(torus_case):
     """Under a permutation of the faces d2 and bary keep their bits and the indices map through it -- except on equal-d2 ties, where
     the smaller NEW index wins and only d2 is compared."""
     verts, faces, points, _ = torus_case
+    permuted(verts, faces, points, "torus 40x20")
+
+
+def permuted(verts, faces, points, what):
     perm = np.random.RandomState(8).permutation(len(faces))
     max_dist = 2 * mean_edge(verts, faces)
     for md in (max_dist, math.inf):
@@ -187,7 +191,7 @@ def test_face_permutation(torus_case):
         tie = mapped != a[0]
         D = SR.pair_d2(points[tie], verts, faces, np.float32)
         rows = np.arange(tie.sum())
-        print(f"permutation, max_dist {md}: {tie.sum()} queries moved to another face")
+        print(f"permutation of {what}, max_dist {md}: {tie.sum()} queries moved to another face")
         assert np.array_equal(D[rows, mapped[tie]], D[rows, a[0][tie]]) and np.array_equal(D[rows, a[0][tie]], a[1][tie])
         assert np.array_equal(bits(a[2][~tie]), bits(b[2][~tie]))
 
@@ -218,3 +222,88 @@ def test_interpolate_and_palette_bit_equal(torus_case):
     host = C.palette(dev(xyz), tuple(float(c) for c in center), float(scale), mode="checker").cpu().numpy()
     assert np.array_equal(bits(host), bits(SR.palette32(xyz, center, scale, "checker", 8)))
     assert C.palette(dev(xyz[:0]), center, scale).shape == (0, 3)
+
+
+# ---- thin faces: marching-cubes spheres, split tori, sliver soups, micro triangles (tests/_surface_ref.py, qualified on the host by
+# tests/test_surface_host.py) ---------------------------------------------------------------------------------------------------------------
+def twice(points, verts, faces, max_dist, want, what):
+    got = run(points, verts, faces, max_dist)
+    same(got, want, what)
+    again = run(points, verts, faces, max_dist)
+    assert np.array_equal(got[0], again[0]) and np.array_equal(bits(got[1]), bits(again[1])) and np.array_equal(bits(got[2]), bits(again[2])), \
+        what + ": a second call returned other bits"
+    return got
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(SR.SLIVER_CASES))
+def test_thin_faces_bit_equal(name):
+    """The brute force and the grid at 0.5, 2 and 10 mean edge lengths -- and, where the input has one sliver height h, at 3 h, between
+    that height and the long edge -- against the statement, each twice.  Every bound leaves some queries unmatched and some not."""
+    c = SR.sliver_case(name)
+    verts, faces, points, ref = c["verts"], c["faces"], c["points"], c["ref"]
+    ok = SR.face_ok(verts, faces)
+    got = twice(points, verts, faces, math.inf, ref, f"{name}, brute force")
+    assert ok[got[0][got[0] >= 0]].all()
+    edge = mean_edge(verts, faces)
+    bounds = [(f"{k} mean edges", k * edge) for k in (0.5, 2.0, 10.0)]
+    if name in SR.SLIVER_HEIGHT:
+        bounds.append(("3 h", 3 * SR.SLIVER_HEIGHT[name]))
+    for label, max_dist in bounds:
+        want = blank(ref, max_dist)
+        assert 0 < (want[0] >= 0).sum() < len(points), label  # the bound cuts
+        got = twice(points, verts, faces, max_dist, want, f"{name}, max_dist {label} = {max_dist:.3e}")
+        assert ok[got[0][got[0] >= 0]].all()
+
+
+@pytest.mark.gpu
+def test_micro_triangles_follow_the_candidate_rule():
+    """Edges from 1e-9 to 1e-22: |n|^2 normal, denormal and 0 in fp32.  The faces the device ever chooses are candidates of the
+    statement (len > 0 with denormals kept: a kernel that flushed them would refuse the 63 faces with a denormal |n|^2), every one of
+    them is chosen by some query, and where the nearest geometry is a refused face the answer is the statement's other face."""
+    c = SR.sliver_case("micro")
+    verts, faces, points, ref = c["verts"], c["faces"], c["points"], c["ref"]
+    ok = SR.face_ok(verts, faces)
+    near64 = SR.closest64(points, verts, faces)[0]
+    print(f"micro: {ok.sum()} of {len(faces)} faces are candidates; the float64 nearest face is a refused one for {(~ok[near64]).sum()} "
+          f"of {len(points)} queries")
+    assert (~ok[near64]).sum() > 100
+    for max_dist in (math.inf, 10 * mean_edge(verts, faces)):
+        got = run(points, verts, faces, max_dist)
+        chosen = np.unique(got[0][got[0] >= 0])
+        assert ok[chosen].all()
+        same(got, blank(ref, max_dist), f"micro, max_dist {max_dist:.3e}")
+        if math.isinf(max_dist):
+            assert len(chosen) == ok.sum()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["mc_sphere_1e-6", "split_torus_1e-6"])
+def test_face_permutation_thin_faces(name):
+    c = SR.sliver_case(name)
+    permuted(c["verts"], c["faces"], c["points"], name)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(SR.SLIVER_CASES))
+def test_face_geometry_shares_the_candidate_rule(name):
+    """anchor.face_geometry on the same inputs: the normal is 0 exactly where the fp32 length of cross(v1 - v0, v2 - v0) is 0 in a
+    numpy statement of its arithmetic -- the len > 0 rule that surface.hip takes over, denormal lengths included -- and the centroids
+    ((v0 + v1) + v2) / 3 keep their bits."""
+    c = SR.sliver_case(name)
+    verts, faces = c["verts"], c["faces"]
+    a, b, cc = verts[faces[:, 0]], verts[faces[:, 1]], verts[faces[:, 2]]
+    with np.errstate(all="ignore"):
+        e1, e2 = b - a, cc - a
+        n = np.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
+                      e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], 1)
+        ln = np.sqrt((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2])
+        unit = np.where(ln[:, None] > 0, n / np.where(ln > 0, ln, np.float32(1))[:, None], np.float32(0))
+        cent = ((a + b) + cc) / np.float32(3)
+    got_c, got_n = (t.cpu().numpy() for t in pkg("anchor").face_geometry(dev(verts), dev(faces)))
+    flat = (got_n == 0).all(1)
+    print(f"{name}: {flat.sum()} of {len(faces)} normals are 0, the statement's length is 0 for {(ln == 0).sum()}; normals differing in "
+          f"bits {(bits(got_n) != bits(unit)).any(1).sum()}, centroids {(bits(got_c) != bits(cent)).any(1).sum()}")
+    assert np.array_equal(flat, ln == 0)
+    assert np.array_equal(SR.face_ok(verts, faces), ~flat & np.isfinite(ln))  # the rule surface.hip shares
+    assert np.array_equal(bits(got_c), bits(cent))
