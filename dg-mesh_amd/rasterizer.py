@@ -213,6 +213,8 @@ def _forward_dispatch(dev, binning, run_sync, run_cap):
     while True:
         cap = INJECT_CAPACITY or st["cap"]
         INJECT_CAPACITY = 0
+        # (dgm_binning_bytes already contains the 256 bytes by which the library aligns the chunk -- tests/test_redzone.py hands the
+        # synchronous entry exactly that size at 128-byte alignment -- so the + 256 here is spare, not needed)
         nbytes = int(_lib.lib().dgm_binning_bytes(cap)) + 256
         run_cap(_fixed_resizer(binning, nbytes), cap, ctypes.c_void_p(st["words"].data_ptr()))
         st["event"].record(torch.cuda.current_stream(dev))

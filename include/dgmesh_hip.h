@@ -35,7 +35,17 @@
  *   - `stream` is a hipStream_t (NULL = default stream).  Unlike the reference (legacy default
  *     stream everywhere) all work is enqueued on the caller's stream;
  *   - outputs are fully OVERWRITTEN (the reference accumulates into pre-zeroed tensors); callers
- *     need not zero-fill out_color, radii or any dL_d* array.
+ *     need not zero-fill out_color, radii or any dL_d* array;
+ *   - memory contracts (tabulated in DESIGN.md "Memory contracts"; tests/test_redzone.py enforces the sizes, the bounds, the initial
+ *     state and 16-byte alignment of byte scratch -- alignment figures below 16 are read from the launchers): a call reads its inputs and
+ *     writes its outputs within exactly the shapes stated here, and touches exactly dgm_*_bytes(...) / dgm_*_floats(...) of a scratch
+ *     buffer from the pointer it is handed -- a size already contains whatever the library needs to align that pointer itself.
+ *     Unless an entry says otherwise a scratch buffer has NO INITIAL STATE (its bytes on entry do not matter, whatever an earlier
+ *     call left there included) and may start at any 16-byte aligned address; tensors of floats / ints need their natural 4-byte
+ *     alignment only (a 16-byte aligned start merely selects a vector code path where one exists, with identical results).  The
+ *     exceptions: dgm_knn_mean_dist2 (256-byte aligned scratch, checked), dgm_ninit_bbox (scratch zero before its first call),
+ *     the (P, 4) float4 arrays of the rasterizer -- rotations, dL_dconic, dL_drot: 16-byte aligned, checked -- and the tables of
+ *     dgm_resample (stated there).
  */
 #ifndef DGMESH_HIP_H
 #define DGMESH_HIP_H
@@ -64,7 +74,9 @@ extern "C" {
 #define DGM_ABI_VERSION 5
 
 /* Allocator callback: must return a device pointer to at least `bytes` bytes (128-byte aligned),
- * valid until the matching backward has run.  Mirrors resizeFunctional, rasterize_points.cu:27-33. */
+ * valid until the matching backward has run.  Mirrors resizeFunctional, rasterize_points.cu:27-33.
+ * `bytes` is exactly dgm_geometry_bytes / dgm_binning_bytes / dgm_image_bytes of the frame; each contains the 256 bytes by which
+ * the library aligns the pointer up, so the caller adds nothing.  The chunks have no initial state. */
 typedef char* (*dgm_alloc_fn)(void* ctx, size_t bytes);
 
 int dgm_abi_version(void);
@@ -139,7 +151,8 @@ int dgm_rasterize_backward_split_sh(int P, int D, int M, int R, const float* bac
 int dgm_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present,
                      void* stream);
 
-/* Sizes of the three scratch buffers (what the allocator callbacks will be asked for). */
+/* Sizes of the three scratch buffers (exactly what the allocator callbacks will be asked for, alignment slack included;
+ * dgm_binning_bytes(R) with the R that *num_rendered receives -- or the capacity, in capacity mode). */
 size_t dgm_geometry_bytes(int P, int width, int height);
 size_t dgm_binning_bytes(int R);
 size_t dgm_image_bytes(int width, int height);
@@ -267,7 +280,9 @@ typedef struct {
 int dgm_mlp_set_gemm(int mode);
 
 /* Bytes of the workspace that forward fills (embedding, the 8 post-ReLU activations, re-laid-out
- * weights, scratch) and backward consumes; caller-owned, must stay alive between the two calls. */
+ * weights, scratch) and backward consumes; caller-owned, must stay alive between the two calls.  The same size in every
+ * arithmetic; any alignment (the library aligns to 256 itself, the size contains that); no initial state for forward, and backward
+ * reads only what its forward wrote. */
 size_t dgm_mlp_workspace_bytes(int N);
 
 /* Introspection for tests and tools: byte offsets of the workspace's per-row tensors for N rows, in this order:
@@ -337,7 +352,8 @@ int dgm_timenet_backward(const float* d_out, int n_freq, const float* W2, int hi
 /* loss = (1 - lambda) * mean|image - gt| + lambda * (1 - mean SSIM(image, gt)), the Gaussian-branch image loss of
  * dgmesh/train.py:307-311 (l1_loss + ssim of dgmesh/utils/loss_utils.py:18-19, 32-76; 11x11 window, sigma 1.5,
  * zero padding).  image, gt: (channels, H, W) fp32 device; out: 3 floats {loss, L1 term, mean SSIM};
- * the workspace filled by forward is consumed by backward.  gt receives no gradient. */
+ * the workspace filled by forward is consumed by backward (any alignment: aligned to 256 by the library, the size contains
+ * that; no initial state for forward).  gt receives no gradient.  H, W >= 1: no minimum size. */
 size_t dgm_image_loss_workspace_bytes(int channels, int H, int W);
 int dgm_image_loss_forward(const float* image, const float* gt, int channels, int H, int W, float lambda_dssim,
                            char* workspace, float* out, void* stream);
@@ -415,7 +431,8 @@ int dgm_se3_transform_backward(int N, const float* T, const float* xyz, const fl
 
 /* Cycle-consistency loss of dgmesh/train.py:221-238 on the raw (N, ld) outputs a (deform) and b (deform_back):
  * out[0] = (mean|b_xyz + a_xyz| + mean|b_rot + a_rot| + mean|b_scale + a_scale|) / 3, out[1..3] the three terms.
- * Fixed-order two-level reduction.  backward: grad_out = device scalar; d_a, d_b (N, ld) fully written. */
+ * Fixed-order two-level reduction.  backward: grad_out = device scalar; d_a, d_b (N, ld) fully written.
+ * workspace: dgm_cycle_loss_workspace_bytes(N) bytes of floats (4-byte aligned), used by the forward only, no initial state. */
 size_t dgm_cycle_loss_workspace_bytes(int N);
 int dgm_cycle_loss_forward(int N, const float* a, const float* b, int ld, char* workspace, float* out, void* stream);
 int dgm_cycle_loss_backward(int N, const float* a, const float* b, int ld, const float* grad_out, float* d_a, float* d_b,
@@ -444,7 +461,9 @@ int dgm_adam_step(int n_tensors, float* const* params, const float* const* grads
  *     [originals | clones | first children | second children] like the reference's cat / prune sequence.
  *   dgm_densify_apply: out[t][j] = in[t][source(j)] for all n_tensors (<= 24) tensors of row width width[t] floats; rows of
  *     new points are zero where is_moment[t] != 0; the xyz / scaling rows of split children are rewritten from the
- *     caller's standard-normal samples z[2][P][3] (device).  src_scratch: (K + C + 2 S) * 4 bytes. */
+ *     caller's standard-normal samples z[2][P][3] (device).  src_scratch: (K + C + 2 S) * 4 bytes.
+ *   scratch: dgm_densify_scratch_bytes(P) bytes, 4-byte aligned, no initial state; _decide writes it (flags, three scans, the totals
+ *     at dgm_densify_totals_offset(P), which is a multiple of 256 and leaves 256 bytes behind it) and _apply of the same P reads it. */
 /* Per-iteration statistics (dgmesh/train.py:489-496, gaussian_model_dpsr_dynamic_anchor.py:679-682), in place, for the
  * Gaussians with radii > 0: max_radii2D = max(max_radii2D, radii); with grad2d != NULL (dL/dmeans2D, (P,3)) also
  * grad_accum += |grad2d[:, :2]| and denom += 1.  All (P) fp32 on the device. */
@@ -478,7 +497,8 @@ int dgm_dpsr_spectral(int res, float sig, const float* in, float* out, int adjoi
 /* Umbrella-operator Laplacian regulariser of a triangle mesh, laplace_regularizer_const (dgmesh/nvdiffrast_utils/regularizer.py:40-60):
  * loss[0] = mean over the 3 V components of (term / max(norm, 1))^2, term[v] = sum over the faces at v of (a - v) + (b - v),
  * norm[v] = 2 x faces at v.  v_pos (V, 3) fp32, faces (F, 3) int32, scratch: dgm_laplace_scratch_floats(V) floats of caller-owned
- * device memory that the backward reads again (normalised term, norm).  dv (V, 3) = dloss[0] x d loss / d v_pos (overwritten).
+ * device memory (no initial state: the forward zeroes what it accumulates into) that the backward reads again (normalised term,
+ * norm).  dv (V, 3) = dloss[0] x d loss / d v_pos (overwritten).  Face indices must lie in [0, V): they are not range-checked.
  * Sums use fp32 atomics like the reference's scatter_add_: results agree to rounding, not bit for bit, run to run. */
 size_t dgm_laplace_scratch_floats(int V);
 int dgm_laplace_forward(int V, int F, const float* v_pos, const int* faces, float* scratch, float* loss, void* stream);
@@ -488,7 +508,9 @@ int dgm_laplace_backward(int V, int F, const int* faces, const float* scratch, c
  * Replaces get_opacity_field_from_gaussians (dgmesh/utils/mesh_utils.py:7-76): occ[res^3] = sum over the Gaussians of the
  * cell's block (centre strictly inside the block's box grown by `margin`, opacity > opacity_threshold) of
  * opacity * exp(-0.5 d^T Sigma^-1 d), Sigma from (scalings, rotations) as build_covariance_from_scaling_rotation,
- * inverse by cofactors + 1e-24 (gaussian_3d_coeff).  coords[res]: the grid coordinates along an axis. */
+ * inverse by cofactors + 1e-24 (gaussian_3d_coeff).  coords[res]: the grid coordinates along an axis.
+ * scratch: dgm_opacity_field_scratch_bytes(P) bytes = 12 floats per Gaussian (4-byte aligned) and 256 spare; no initial state;
+ * not read for P == 0.  res need not be a multiple of num_blocks: the last block of an axis is shorter, as torch's split. */
 size_t dgm_opacity_field_scratch_bytes(int P);
 int dgm_opacity_field(int P, const float* xyz, const float* rotations, const float* scalings, const float* opacities,
                       float opacity_threshold, int res, int num_blocks, float margin, const float* coords, char* scratch,
@@ -504,7 +526,8 @@ int dgm_opacity_field(int P, const float* xyz, const float* rotations, const flo
  * (csrc/mc_tables.hpp, generated by tools/gen_mc_tables.py), wound so that (v1 - v0) x (v2 - v0) points towards f >= iso.
  * All orders come from prefix sums: output is identical run to run.
  *   dgm_mc_scratch_bytes: caller-owned device scratch for one extraction (0 for invalid dimensions); count, emit and backward of
- *                         one extraction use the same scratch, and the grid must not change between them.
+ *                         one extraction use the same scratch, and the grid must not change between them.  16-byte aligned (the
+ *                         arrays inside sit at multiples of 256 from the pointer as given); no initial state for count.
  *   dgm_mc_count   : classifies the cells and writes counts[0] = V, counts[1] = F (device ints).  The caller reads them back
  *                    (the extraction's one host synchronisation) and sizes the outputs.
  *   dgm_mc_emit    : writes verts (V, 3) fp32 and faces (F, 3) int32 (V, F: the counts; NULL allowed where a count is 0).
@@ -523,14 +546,16 @@ int dgm_mc_backward(int X, int Y, int Z, const float* grid, const float* deform,
  * is centred at (px + .5, py + .5), row 0 at NDC y = -1.  A face with a vertex at w <= 0 (or an index outside [0, V), or zero
  * screen area) is dropped.  A centre is covered when the three oriented edge functions, each evaluated with its endpoints in
  * ascending vertex-id order, are >= 0.  Depth z/w, linear in screen space; the smaller wins, ties to the lower face id.
- *   dgm_tri_raster_scratch_bytes: device scratch of one rasterize forward (0 for invalid sizes).
+ *   dgm_tri_raster_scratch_bytes: device scratch of one rasterize forward (0 for invalid sizes): 64-bit keys first, so 8-byte
+ *                               aligned at least; no initial state (the forward clears it); not needed by the backward.
  *   dgm_tri_rasterize_forward : rast (H, W, 4) = (u, v, z/w, id + 1), zeros on background; (u, v) perspective-correct
  *                               barycentrics of vertices 0 and 1.  Bit-reproducible.
  *   dgm_tri_rasterize_backward: dpos (V, 4) (overwritten) = the gradient of sum(drast[..., 0:2] * rast[..., 0:2]) w.r.t. x, y, w;
  *                               the z column is zero.
  *   dgm_tri_interpolate_*     : out (H, W, C) = u a0 + v a1 + (1 - u - v) a2 (zeros on background); backward writes dattr (V, C)
  *                               and drast (H, W, 4) (channels 2, 3 zero), both overwritten.
- *   dgm_tri_aa_scratch_bytes: device scratch of one antialias forward (the edge topology); its backward reads it again.
+ *   dgm_tri_aa_scratch_bytes: device scratch of one antialias forward (the edge topology); its backward reads it again.  8-byte
+ *                               aligned at least; no initial state for the forward.
  *   dgm_tri_antialias_forward : out (H, W, C) = color + the analytic blend across silhouette edges (csrc/mesh_raster.hip).
  *                               Bit-reproducible.
  *   dgm_tri_antialias_backward: dcolor (H, W, C) (a gather, bit-reproducible) and dpos (V, 4) (overwritten).
@@ -615,8 +640,9 @@ int dgm_ninit_sample(int V, int F, int count, const float* verts, const int* fac
  *       (size odd, 1..15).  Per pixel the smallest z/w wins, ties to the lower point id: one 64-bit atomicMin of
  *       (ordered z/w bits) << 32 | id.  image (H, W, 3) = the winner's colour -- colors (N, 3), or, when colors is NULL,
  *       bg_color6[3..5] -- and bg_color6[0..2] elsewhere; bg_color6 is a HOST array of six floats.  Bit-reproducible.
- *       scratch: dgm_point_splat_scratch_bytes(H, W) bytes (0 for invalid sizes); after the call its first H W uint64 hold the winning
- *       keys (all ones: empty; low 32 bits: the point id).
+ *       scratch: dgm_point_splat_scratch_bytes(H, W) bytes (0 for invalid sizes) = H W uint64 rounded up to 256, used from the
+ *       pointer as given: it must be 8-byte aligned (64-bit atomics; the size holds no alignment slack), no initial state (the call
+ *       sets it to all ones); after the call its first H W uint64 hold the winning keys (all ones: empty; low 32 bits: the point id).
  *   dgm_compose_frame: n_panels (1..4) fp32 panels of H x W pixels, panels[k] (a HOST array of device pointers) laid out (3, H, W)
  *       when layouts[k] (HOST) is 0 and (H, W, 3) when it is 1, side by side into out_u8 (H/d, n_panels W/d, 3) uint8.  d = downsample
  *       is 1 or 2 (then H and W are even): each 2x2 block averages as ((a + b) + (c + d)) * 0.25, top row first.  Then
@@ -655,7 +681,8 @@ int dgm_compose_frame(int n_panels, const float* const* panels, const int* layou
  *       ct = ceil(cols / tile 1), want = min(ct, ceil(tile 2 / rt)), each part takes ceil(ct / want) column tiles.  0 for sizes
  *       outside [1, 2^28].
  *   dgm_emd_scratch_floats: the caller-owned scratch of one call, in floats: five vectors of b n or b m floats and the partial
- *       sums, b max(2 n parts(n, m), m parts(m, n)) floats; 0 for invalid sizes.  Its contents on entry do not matter.
+ *       sums, b max(2 n parts(n, m), m parts(m, n)) floats, each rounded up to 64 floats; 0 for invalid sizes.  Its contents on entry
+ *       do not matter; 4-byte aligned.
  *   dgm_emd_approx: cost (b) = sum over the nine levels of sum w[k,l] sqrt(d2[k,l]) (not divided by n); residual (b, 2), unless
  *       NULL, = (sum remainL, sum remainR) after the last level, the mass that was not transported.  1 <= b <= 65535,
  *       1 <= n, m <= 2^28: row, column and tile indices are int, which that cap keeps far from overflow; every buffer offset
