@@ -207,8 +207,9 @@ class MeshPhase:
         """phi of the deformed Gaussians, signed and shifted by the density threshold (R/utils/renderer.py:150-168): (R, R, R), the
         surface at 0.  deform / deform_normal: the networks' outputs at the Gaussians (d_xyz (P, 3), d_normal (P, 3)) or None;
         freeze_pos: no gradient to the positions (the normal warm-up)."""
-        pts = g.get_xyz.detach() + deform.detach() if freeze_pos and deform is not None else (
-            g.get_xyz + deform if deform is not None else g.get_xyz)
+        pts = g.get_xyz.detach() if freeze_pos else g.get_xyz                            # (frozen with or without a deformation)
+        if deform is not None:
+            pts = pts + (deform.detach() if freeze_pos else deform)
         pts = ((pts - g.gaussian_center) / g.gaussian_scale) / 2.0 + 0.5
         pts = torch.clamp(pts, 1e-6, 1 - 1e-6)
         normals = g.get_normal + deform_normal if deform_normal is not None else g.get_normal

@@ -1,6 +1,7 @@
 """Plain float64 torch restatement of the mesh rasterizer (dg-mesh_amd/mesh_raster.py, csrc/mesh_raster.hip): brute-force
 coverage and depth over every pixel x triangle, perspective-correct barycentrics, interpolate and the antialias rule, with
-autograd standing in for every adjoint.  Runs on the CPU (or any device); no HIP.
+autograd standing in for every adjoint.  Runs on the CPU (or any device); no HIP.  The differentiable passes take a `dtype`
+(default float64; float32 gives a single-precision run of the same arithmetic); rasterize_ids is always float64.
 
 pos (V, 4) clip space, tri (F, 3); screen s = ((x/w + 1) W/2, (y/w + 1) H/2), pixel centres at (px + .5, py + .5)."""
 import torch
@@ -8,8 +9,8 @@ import torch
 D = torch.float64
 
 
-def screen(pos, H, W):
-    pos = pos.to(D)
+def screen(pos, H, W, dtype=D):
+    pos = pos.to(dtype)
     w = pos[:, 3]
     return (pos[:, 0] / w + 1.0) * (0.5 * W), (pos[:, 1] / w + 1.0) * (0.5 * H), pos[:, 2] / w
 
@@ -94,17 +95,20 @@ def rasterize_ids(pos, tri, H, W, x0=0, y0=0, w=None, h=None, tol=1e-4, chunk=1 
     return bid.reshape(h, w), torch.where(bid > 0, best, torch.zeros_like(best)).reshape(h, w), fragile.reshape(h, w)
 
 
-def barycentrics(pos, tri, ids, H, W, x0=0, y0=0):
+def barycentrics(pos, tri, ids, H, W, x0=0, y0=0, dtype=D):
     """Differentiable in pos: (u, v) (h, w) perspective-correct barycentrics of vertices 0 and 1 of the face `ids` names
-    (0: background -> 0), and z/w."""
+    (0: background -> 0), and z/w.  dtype: the precision of the arithmetic (float64, or float32 for a single-precision run)."""
     h, w = ids.shape
+    D = dtype
     pos = pos.to(D)
     tri = tri.long()
     sel = ids.flatten() > 0
     f = (ids.flatten()[sel] - 1)
-    yy, xx = torch.meshgrid(torch.arange(y0, y0 + h, dtype=D), torch.arange(x0, x0 + w, dtype=D), indexing="ij")
+    dev = pos.device
+    yy, xx = torch.meshgrid(torch.arange(y0, y0 + h, dtype=D, device=dev), torch.arange(x0, x0 + w, dtype=D, device=dev),
+                            indexing="ij")
     px, py = (xx + 0.5).flatten()[sel], (yy + 0.5).flatten()[sel]
-    sx, sy, zw = screen(pos, H, W)
+    sx, sy, zw = screen(pos, H, W, D)
     t = tri[f]
     E = []
     for k in range(3):
@@ -114,14 +118,14 @@ def barycentrics(pos, tri, ids, H, W, x0=0, y0=0):
     S = e[0] + e[1] + e[2]
     Ds = E[0] + E[1] + E[2]
     z = (E[0] * zw[t[:, 0]] + E[1] * zw[t[:, 1]] + E[2] * zw[t[:, 2]]) / Ds
-    out = torch.zeros((h * w, 3), dtype=D)
+    out = torch.zeros((h * w, 3), dtype=D, device=dev)
     out = out.index_put((torch.nonzero(sel).flatten(),), torch.stack([e[0] / S, e[1] / S, z], 1))
     return out[:, 0].reshape(h, w), out[:, 1].reshape(h, w), out[:, 2].reshape(h, w)
 
 
-def interpolate(attr, u, v, ids, tri):
+def interpolate(attr, u, v, ids, tri, dtype=D):
     """out (h, w, C) = u a0 + v a1 + (1 - u - v) a2 on covered pixels, 0 on background (differentiable in attr, u, v)."""
-    attr = attr.to(D)
+    attr = attr.to(dtype)
     tri = tri.long()
     f = (ids - 1).clamp_min(0)
     t = tri[f]
@@ -130,20 +134,20 @@ def interpolate(attr, u, v, ids, tri):
     return torch.where((ids > 0)[..., None], out, torch.zeros_like(out))
 
 
-def silhouette_flags(pos, tri, H, W):
+def silhouette_flags(pos, tri, H, W, dtype=D):
     """(F, 3) bool: edge k of face f is a silhouette (one face; more than two; two whose third vertices lie on the same screen side
     or on the edge's line)."""
     tri = tri.long()
     F = tri.shape[0]
     if F == 0:
-        return torch.zeros((0, 3), dtype=torch.bool)
-    sx, sy, _ = screen(pos.detach(), H, W)
+        return torch.zeros((0, 3), dtype=torch.bool, device=tri.device)
+    sx, sy, _ = screen(pos.detach(), H, W, dtype)
     a = torch.stack([tri[:, (k + 1) % 3] for k in range(3)], 1)
     b = torch.stack([tri[:, (k + 2) % 3] for k in range(3)], 1)
     c = tri
     key = torch.minimum(a, b) * (1 << 32) + torch.maximum(a, b)
     uniq, inv, cnt = torch.unique(key.flatten(), return_inverse=True, return_counts=True)
-    sumc = torch.zeros(uniq.numel(), dtype=torch.long).index_add_(0, inv, c.flatten())
+    sumc = torch.zeros(uniq.numel(), dtype=torch.long, device=tri.device).index_add_(0, inv, c.flatten())
     other = (sumc[inv] - c.flatten()).reshape(F, 3).clamp(0, max(pos.shape[0] - 1, 0))
     n = cnt[inv].reshape(F, 3)
     Ec = _edge(sx[a], sy[a], sx[b], sy[b], sx[c], sy[c])
@@ -152,20 +156,22 @@ def silhouette_flags(pos, tri, H, W):
     return (n != 2) | ~opposite
 
 
-def antialias(color, ids, zw, pos, tri, H, W):
+def antialias(color, ids, zw, pos, tri, H, W, dtype=D):
     """The antialias rule on the whole image (ids, zw (H, W); color (H, W, C)), differentiable in color and pos: returns out
     (H, W, C)."""
+    D = dtype
     color = color.to(D)
     pos = pos.to(D)
     tri = tri.long()
-    sil = silhouette_flags(pos, tri, H, W)
-    sx, sy, _ = screen(pos, H, W)
-    yy, xx = torch.meshgrid(torch.arange(H, dtype=D), torch.arange(W, dtype=D), indexing="ij")
+    sil = silhouette_flags(pos, tri, H, W, D)
+    sx, sy, _ = screen(pos, H, W, D)
+    dev = pos.device
+    yy, xx = torch.meshgrid(torch.arange(H, dtype=D, device=dev), torch.arange(W, dtype=D, device=dev), indexing="ij")
     cx, cy = (xx + 0.5).flatten(), (yy + 0.5).flatten()
     idf, zf = ids.flatten(), zw.flatten().to(D)
     out = color.reshape(H * W, -1).clone()
     cflat = color.reshape(H * W, -1)
-    lin = torch.arange(H * W).reshape(H, W)
+    lin = torch.arange(H * W, device=dev).reshape(H, W)
     for vertical in (False, True):
         p = (lin[:-1, :] if vertical else lin[:, :-1]).flatten()
         q = p + (W if vertical else 1)
@@ -175,7 +181,7 @@ def antialias(color, ids, zw, pos, tri, H, W):
         pf, po = torch.where(qf, q, p), torch.where(qf, p, q)
         T = (torch.where(qf, iq, ip) - 1).clamp_min(0)
         hit = torch.zeros_like(diff)
-        tval = torch.zeros(p.numel(), dtype=D)
+        tval = torch.zeros(p.numel(), dtype=D, device=dev)
         for k in range(3):
             a, b = tri[T, (k + 1) % 3], tri[T, (k + 2) % 3]
             dx, dy = (sx[b] - sx[a]).detach(), (sy[b] - sy[a]).detach()
@@ -199,10 +205,10 @@ def antialias(color, ids, zw, pos, tri, H, W):
     return out.reshape(color.shape)
 
 
-def render_chain(pos, tri, attr, H, W, ids=None, zw=None):
+def render_chain(pos, tri, attr, H, W, ids=None, zw=None, dtype=D):
     """rasterize -> interpolate -> antialias end to end (ids / zw: the discrete part, default from rasterize_ids)."""
     if ids is None:
         ids, zw, _ = rasterize_ids(pos, tri, H, W)
-    u, v, z = barycentrics(pos, tri, ids, H, W)
-    col = interpolate(attr, u, v, ids, tri)
-    return antialias(col, ids, zw if zw is not None else z.detach(), pos, tri, H, W), ids
+    u, v, z = barycentrics(pos, tri, ids, H, W, dtype=dtype)
+    col = interpolate(attr, u, v, ids, tri, dtype)
+    return antialias(col, ids, zw if zw is not None else z.detach(), pos, tri, H, W, dtype), ids
