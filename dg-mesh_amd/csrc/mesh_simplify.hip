@@ -29,6 +29,7 @@
 #include <stdio.h>
 
 #include "dgm_common.hpp"
+#include "mesh_scan.hpp"
 
 #pragma clang fp contract(off)
 
@@ -42,6 +43,7 @@ using namespace dgm;
 constexpr int SP_THREADS = 256;
 constexpr int SP_ITEMS = 16;
 constexpr int SP_TILE = SP_THREADS * SP_ITEMS;  // integers per workgroup of the offset scan: its fixed partition
+static_assert(SP_TILE == SCAN_TILE, "the scratch layout counts the tiles of mesh_scan.hpp");
 constexpr int SP_WAVES = SP_THREADS / 64;
 constexpr int SP_MAX_DIM = 1 << 20;
 constexpr unsigned long long KEY_EMPTY = ~0ull;
@@ -360,80 +362,6 @@ sp_inst_count_kernel(int V, int F, const int* __restrict__ rep_faces, unsigned* 
         if (r[k] >= 0 && r[k] < V) atomicAdd(count + r[k], 1u);
 }
 
-__device__ __forceinline__ unsigned tile_prefix(long long n, const unsigned* __restrict__ val, long long base, unsigned* x, unsigned* lds,
-                                                unsigned& total) {
-    unsigned s = 0;
-#pragma unroll
-    for (int k = 0; k < SP_ITEMS; k++) {
-        x[k] = base + k < n ? val[base + k] : 0u;
-        s += x[k];
-    }
-    const unsigned inc = wave_inclusive_scan_u32(s);
-    const int wv = threadIdx.x >> 6;
-    if (lane_id() == 63) lds[wv] = inc;
-    __syncthreads();
-    unsigned before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < SP_WAVES; w++) {
-        const unsigned t = lds[w];
-        if (w < wv) before += t;
-        all += t;
-    }
-    __syncthreads();
-    total = all;
-    return before + inc - s;
-}
-
-__global__ void __launch_bounds__(SP_THREADS)
-sp_scan_totals_kernel(long long n, const unsigned* __restrict__ val, unsigned* __restrict__ tile_total) {
-    __shared__ unsigned lds[SP_WAVES];
-    unsigned x[SP_ITEMS], total;
-    tile_prefix(n, val, (long long)blockIdx.x * SP_TILE + (long long)threadIdx.x * SP_ITEMS, x, lds, total);
-    if (threadIdx.x == 0) tile_total[blockIdx.x] = total;
-}
-
-// one workgroup: exclusive offsets of the tiles, added in tile order; total[0] = the sum
-__global__ void __launch_bounds__(SP_THREADS)
-sp_scan_offsets_kernel(int nb, const unsigned* __restrict__ tile_total, unsigned* __restrict__ tile_off, unsigned* __restrict__ total) {
-    __shared__ unsigned lds[SP_THREADS];
-    __shared__ unsigned carry;
-    if (threadIdx.x == 0) carry = 0;
-    for (int base = 0; base < nb; base += SP_THREADS) {  // (ends: base grows by a constant)
-        const int i = base + (int)threadIdx.x;
-        lds[threadIdx.x] = i < nb ? tile_total[i] : 0u;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            unsigned run = carry;
-            for (int t = 0; t < SP_THREADS; t++) {
-                const unsigned v = lds[t];
-                lds[t] = run;
-                run += v;
-            }
-            carry = run;
-        }
-        __syncthreads();
-        if (i < nb) tile_off[i] = lds[threadIdx.x];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) total[0] = carry;
-}
-
-__global__ void __launch_bounds__(SP_THREADS)
-sp_scan_apply_kernel(long long n, const unsigned* __restrict__ val, const unsigned* __restrict__ tile_off, unsigned* __restrict__ offset,
-                     unsigned* __restrict__ cursor) {
-    __shared__ unsigned lds[SP_WAVES];
-    unsigned x[SP_ITEMS], total;
-    const long long base = (long long)blockIdx.x * SP_TILE + (long long)threadIdx.x * SP_ITEMS;
-    unsigned at = tile_off[blockIdx.x] + tile_prefix(n, val, base, x, lds, total);
-#pragma unroll
-    for (int k = 0; k < SP_ITEMS; k++) {
-        if (base + k >= n) break;
-        offset[base + k] = at;
-        cursor[base + k] = 0u;
-        at += x[k];
-    }
-}
-
 __global__ void __launch_bounds__(SP_THREADS)
 sp_inst_fill_kernel(int V, int F, const int* __restrict__ rep_faces, const unsigned* __restrict__ offset, unsigned* __restrict__ cursor,
                     unsigned long long cap, int* __restrict__ inst_face, int* __restrict__ inst_rep) {
@@ -709,14 +637,10 @@ int dgm_mesh_simplify_place(int V, int F, const float* verts, const int* faces, 
     hipStream_t st = (hipStream_t)stream;
     const SimplifyScratch s = simplify_layout(scratch, V, F);
     const Grid g = {ox, oy, oz, h, nx, ny, nz};
-    const int nb = tiles(V);
     unsigned* total = s.box + 8;
     if (hipMemsetAsync(s.count, 0, (size_t)V * 4, st) != hipSuccess) return sdone();
     if (F > 0) hipLaunchKernelGGL(sp_inst_count_kernel, dim3(blocks(F)), dim3(SP_THREADS), 0, st, V, F, rep_faces, s.count);
-    hipLaunchKernelGGL(sp_scan_totals_kernel, dim3(nb), dim3(SP_THREADS), 0, st, (long long)V, (const unsigned*)s.count, s.tile_total);
-    hipLaunchKernelGGL(sp_scan_offsets_kernel, dim3(1), dim3(SP_THREADS), 0, st, nb, (const unsigned*)s.tile_total, s.tile_off, total);
-    hipLaunchKernelGGL(sp_scan_apply_kernel, dim3(nb), dim3(SP_THREADS), 0, st, (long long)V, (const unsigned*)s.count,
-                       (const unsigned*)s.tile_off, s.offset, s.cursor);
+    scan_exclusive(st, (long long)V, (const unsigned*)s.count, s.tile_total, s.tile_off, s.offset, s.cursor, total);
     if (F > 0) {
         hipLaunchKernelGGL(sp_inst_fill_kernel, dim3(blocks(F)), dim3(SP_THREADS), 0, st, V, F, rep_faces, (const unsigned*)s.offset, s.cursor,
                            3ull * (unsigned long long)F, s.inst_face, s.inst_rep);

@@ -86,7 +86,7 @@ def _mesh_view(mesh, gaussians, deform_back, d_xyz, d_normal, cam, white_backgro
 
 @torch.no_grad()
 def testing(gaussians, deform, deform_back, cameras, *, pipe, background, mesh=None, deform_normal=None, is_6dof=False,
-            white_background=True, out_dir=None, save_meshes=False, lpips=None, clean=None, simplify=None):
+            white_background=True, out_dir=None, save_meshes=False, lpips=None, clean=None, simplify=None, smooth=None):
     """testing() of R/train.py:559-761 without the image / glb files.  Per camera: deform.step at the camera's
     fid, scene.render clamped to [0, 1]; with `mesh` (a trainer.MeshPhase that has a DPSR module) also mesh.psr -> mesh.surface ->
     deform_back + mesh.appearance on the vertices -> mesh_raster.render_mesh (deform_normal: the network whose first output is added
@@ -103,7 +103,8 @@ def testing(gaussians, deform, deform_back, cameras, *, pipe, background, mesh=N
     (or a dict of its fields): the components that fail it are removed from the WRITTEN mesh only (mesh_clean.clean_mesh, the colours
     gathered with its vertex index); the mesh image and its metrics are those of the full mesh.  simplify: None, or a
     mesh_simplify.SimplifySpec (or a dict of its fields): the WRITTEN mesh only is decimated by quadric vertex clustering, after
-    `clean`, the colours taken at the representatives.
+    `clean`, the colours taken at the representatives.  smooth: None, or a mesh_smooth.SmoothSpec (or a dict of its fields): the
+    WRITTEN mesh only is smoothed (mesh_smooth.smooth_mesh), after `clean` and BEFORE `simplify` -- denoised first, decimated after.
 
     lpips: None, or {"alex": lpips.LPIPS, "vgg": lpips.LPIPS} with either key optional.  Each network then scores both images of a
     view against the target in one call (the target's features are computed once) into a second device-side table that the same
@@ -154,9 +155,10 @@ def testing(gaussians, deform, deform_back, cameras, *, pipe, background, mesh=N
         for j, net in enumerate(nets):
             lpips[net]._into(*LP._checked(images, gt, net), lp_table[idx, j, :images.shape[0]])
         if save_meshes:
-            from . import mesh_clean, mesh_simplify
+            from . import mesh_clean, mesh_simplify, mesh_smooth
             from .ply_io import write_mesh_ply
             w_verts, w_faces, w_color = mesh_clean.apply(clean, verts, faces, vtx_color)
+            w_verts, w_faces, w_color = mesh_smooth.apply(smooth, w_verts, w_faces, w_color)
             w_verts, w_faces, w_color = mesh_simplify.apply(simplify, w_verts, w_faces, w_color)
             write_mesh_ply(os.path.join(saving_path, "dynamic_mesh", f"frame_{idx}.ply"), w_verts, w_faces, vertex_colors=w_color)
     torch.cuda.synchronize(dev)

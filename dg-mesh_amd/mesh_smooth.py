@@ -1,0 +1,162 @@
+"""Smoothing an extracted mesh on the device: Taubin's lambda | mu scheme ("A signal processing approach to fair surface design",
+SIGGRAPH 1995) and plain Laplacian smoothing with uniform weights, on the sorted adjacency of mesh_topology, as the smoothing kernel
+of csrc/mesh_edges.hip.  A mesh extracted from a grid carries grid-aligned staircase noise; vertex
+clustering (mesh_simplify) keeps it.  Taubin's two steps per iteration -- lambda > 0 shrinks, mu < -lambda inflates -- remove the
+high frequencies without the shrinkage of the Laplacian alone.  trimesh, Open3D and pymeshlab are neither vendored nor dependencies.
+
+Definitions (this project's; include/dgmesh_hip.h states them for the C ABI, tests/_edges_ref.py restates them in numpy):
+  * one step with factor f, for vertex i with neighbour set N (the distinct vertices that share a valid face's side with i):
+    m = (the sum of the neighbours in fp64, from 0, in ascending neighbour order) / (double)|N|; out = (float)(x + f (m - x)) with
+    x = (double)in[i]: one rounding to fp32 per step and coordinate;
+  * a vertex with an empty N (no valid face uses it) and a vertex with a non-finite coordinate are copied unchanged.  A non-finite
+    NEIGHBOUR is not left out of the sum: the vertices next to a NaN vertex become NaN in the first step (IEEE arithmetic) and are
+    then copied themselves, so a NaN spreads by one ring of neighbours per step -- clean such a mesh first;
+  * boundary "fixed": a vertex on a boundary edge (mesh_topology's vert_flag bit 1) is copied unchanged; "curve": for such a vertex N
+    is restricted to the neighbours it is joined to by a boundary edge, so a rim is smoothed along itself; "free": no distinction;
+  * method "taubin": per iteration a step with f = lam and a step with f = mu; "laplacian": a step with f = lam.
+Faces are untouched, so per-vertex attributes need no remapping.  Every output is identical bit for bit from run to run and equal to
+the numpy restatement.  fp32 vertices, int32 faces, CUDA/HIP tensors only -- no CPU fallback.  One 32-byte read-back per call (the
+sizes of the edge table).
+
+Command line: python -m dgmesh_amd.mesh_smooth in.ply out.ply [--iterations N] [--lam L] [--mu M] [--method taubin|laplacian]
+[--boundary fixed|curve|free] reads and writes ply_io's triangle-mesh PLY and keeps vertex colours."""
+import argparse
+import ctypes
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _lib
+
+METHODS = ("taubin", "laplacian")
+BOUNDARIES = ("fixed", "curve", "free")  # the int of the C ABI is the index
+
+
+@dataclass(frozen=True)
+class SmoothSpec:
+    """The parameters of smooth_mesh."""
+    iterations: int = 10
+    lam: float = 0.5
+    mu: float = -0.53
+    method: str = "taubin"
+    boundary: str = "fixed"
+
+    def describe(self):
+        return f"iterations {int(self.iterations)} lam {float(self.lam):g} mu {float(self.mu):g} method {self.method} boundary {self.boundary}"
+
+
+def as_spec(smooth):
+    """None, a SmoothSpec or a dict of its fields -> SmoothSpec or None ("do nothing")."""
+    if smooth is None or isinstance(smooth, SmoothSpec):
+        return smooth
+    if isinstance(smooth, dict):
+        return SmoothSpec(**smooth)
+    raise TypeError(f"mesh_smooth: smooth must be None, a SmoothSpec or a dict of its fields, got {type(smooth).__name__}")
+
+
+def _vp(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else ctypes.c_void_p(0)
+
+
+def _mesh(verts, faces):
+    for t in (verts, faces):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError("mesh_smooth.smooth_mesh needs CUDA/HIP tensors (dg-mesh_amd has no CPU path)")
+    if verts.dtype != torch.float32 or faces.dtype != torch.int32:
+        raise RuntimeError(f"mesh_smooth.smooth_mesh: verts must be float32 and faces int32, got {verts.dtype} and {faces.dtype}")
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"mesh_smooth.smooth_mesh: verts must be (V, 3) and faces (F, 3), got {tuple(verts.shape)} and {tuple(faces.shape)}")
+    if verts.device != faces.device:
+        raise ValueError(f"mesh_smooth.smooth_mesh: verts on {verts.device}, faces on {faces.device}")
+    return verts.detach().contiguous(), faces.detach().contiguous()
+
+
+def _choice(iterations, lam, mu, method, boundary):
+    if method not in METHODS:
+        raise ValueError(f"mesh_smooth: method must be one of {', '.join(METHODS)}, got {method!r}")
+    if boundary not in BOUNDARIES:
+        raise ValueError(f"mesh_smooth: boundary must be one of {', '.join(BOUNDARIES)}, got {boundary!r}")
+    if int(iterations) != iterations or int(iterations) < 0:
+        raise ValueError(f"mesh_smooth: iterations must be an integer >= 0, got {iterations}")
+    if not 0.0 < float(lam) <= 1.0:
+        raise ValueError(f"mesh_smooth: lam must be in (0, 1], got {lam}")
+    if method == "taubin" and not (float(mu) < -float(lam) and np.isfinite(float(mu))):
+        raise ValueError(f"mesh_smooth: Taubin smoothing needs a finite mu < -lam = {-float(lam):g}, got mu = {mu}")
+
+
+def step_factors(iterations, lam, mu, method):
+    """The factor of every step, in order."""
+    return [float(lam), float(mu)] * int(iterations) if method == "taubin" else [float(lam)] * int(iterations)
+
+
+def smooth_mesh(verts, faces, *, iterations=10, lam=0.5, mu=-0.53, method="taubin", boundary="fixed"):
+    """New vertices (V, 3) after `iterations` iterations of `method` (module docstring); the inputs are not modified and faces stay
+    as they are.  iterations = 0 returns `verts` itself.  ValueError names iterations < 0, lam outside (0, 1] and, for Taubin,
+    mu >= -lam."""
+    _choice(iterations, lam, mu, method, boundary)
+    given = verts
+    verts, faces = _mesh(verts, faces)
+    factors = step_factors(iterations, lam, mu, method)
+    V = int(verts.shape[0])
+    if not factors or V == 0:
+        return given
+    from .mesh_topology import EdgeTable
+    table = EdgeTable("smooth_mesh", faces, V)
+    t = table.emit(edges=False, adjacency=True, kind=boundary == "curve")
+    L, dev, A = table.L, table.dev, 2 * table.E
+    src, dst = verts, torch.empty_like(verts)
+    spare = torch.empty_like(verts) if len(factors) > 1 else None  # (the input is never written: the steps alternate between two others)
+    with _lib.device_guard(dev):
+        st = _lib.stream_ptr()
+        for f in factors:
+            _lib.check(L.dgm_mesh_smooth_step(V, A, _vp(src), _vp(table.adj_offset), _vp(t["adj"]), _vp(t["adj_kind"]), _vp(table.vert_flag),
+                                              f, BOUNDARIES.index(boundary), _vp(dst), st))
+            src, dst = dst, (spare if src is verts else src)
+    return src
+
+
+def apply(smooth, verts, faces, *attributes):
+    """smooth (as_spec) applied to a mesh: (verts', faces, *attributes) -- smoothing moves vertices only, so faces and per-vertex
+    attributes pass through; the inputs themselves when smooth is None."""
+    spec = as_spec(smooth)
+    if spec is None:
+        return (verts, faces) + attributes
+    v = smooth_mesh(verts, faces, iterations=spec.iterations, lam=spec.lam, mu=spec.mu, method=spec.method, boundary=spec.boundary)
+    return (v, faces) + attributes
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(prog="python -m dgmesh_amd.mesh_smooth",
+                                 description="Smooth a triangle-mesh PLY on the GPU (Taubin lambda | mu or plain Laplacian).")
+    ap.add_argument("input")
+    ap.add_argument("output")
+    ap.add_argument("--iterations", type=int, default=10)
+    ap.add_argument("--lam", type=float, default=0.5)
+    ap.add_argument("--mu", type=float, default=-0.53)
+    ap.add_argument("--method", choices=METHODS, default="taubin")
+    ap.add_argument("--boundary", choices=BOUNDARIES, default="fixed")
+    return ap
+
+
+def spec_from_args(args):
+    return SmoothSpec(iterations=args.iterations, lam=args.lam, mu=args.mu, method=args.method, boundary=args.boundary)
+
+
+def main(argv=None):
+    from .ply_io import read_mesh_ply, write_mesh_ply
+    args = build_parser().parse_args(argv)
+    spec = spec_from_args(args)
+    _choice(spec.iterations, spec.lam, spec.mu, spec.method, spec.boundary)
+    verts, faces, colors = read_mesh_ply(args.input, return_colors=True)
+    dev = torch.device("cuda")
+    v = apply(spec, torch.from_numpy(verts).to(dev), torch.from_numpy(faces).to(dev))[0]
+    # (write_mesh_ply quantises floats in [0, 1] as clip(c * 255) truncated: (k + 0.5) / 255 gives k back for every byte k)
+    same_colors = None if colors is None else (colors[:, :3].astype(np.float32) + np.float32(0.5)) / np.float32(255.0)
+    write_mesh_ply(args.output, v, faces, vertex_colors=same_colors)
+    print(f"mesh_smooth: V {len(verts)} F {len(faces)}  {spec.describe()}")
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

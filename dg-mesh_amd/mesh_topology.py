@@ -1,0 +1,175 @@
+"""The edge table of a triangle mesh on the device and what it says about the mesh: unique edges, the faces on either side of them,
+per-vertex sorted adjacency, boundary / non-manifold / misoriented edges, watertightness, Euler characteristic and genus -- kernels
+of csrc/mesh_edges.hip.  The reference builds its edge list and edge -> face map with torch.unique
+(R/nvdiffrast_utils/mesh.py:97-149; R/ = dgmesh/); trimesh, Open3D and pymeshlab are neither vendored nor dependencies.
+
+Definitions (this project's; include/dgmesh_hip.h states them for the C ABI, tests/_edges_ref.py restates them in numpy):
+  * a face is valid iff its three indices are in [0, V) and pairwise different (mesh_clean's definition; coordinates play no part);
+    a valid face (a, b, c) traverses the directed half-edges a->b, b->c, c->a; a vertex is used when a valid face uses it;
+  * edges (E, 2) int32: the distinct sides of the valid faces as u < v, in lexicographic order -- on a mesh of valid faces what the
+    reference's compute_edges returns;
+  * edge_count (E, 2): the valid faces that traverse u->v and v->u; edge_faces (E, 2): the smallest index among them, -1 for none;
+  * an edge is a boundary edge when its counts sum to 1, misoriented when they are (2, 0) or (0, 2), non-manifold when they sum to 3
+    or more, regular when they are (1, 1);
+  * adj_offset (V + 1,), adj (2E,): the distinct neighbours of every vertex, ascending; adj_kind (2E,) uint8 the class of the edge to
+    each (0 regular, 1 boundary, 2 non-manifold, 3 misoriented);
+  * vert_flag (V,) uint8: bit 0 used, bit 1 on a boundary edge, bit 2 on a non-manifold or misoriented edge.
+Everything is integers: the results are identical bit for bit from run to run.  int32 faces, CUDA/HIP tensors only -- no CPU fallback.
+Host read-backs: 32 bytes per edge table (the sizes and class counts, between the count and the emit call); topology_report adds 8
+bytes for the out-of-range faces of connected_components, 8 for the components and 12 for the edge lengths.
+
+Command line: python -m dgmesh_amd.mesh_topology mesh.ply [...] prints one JSON report per file."""
+import argparse
+import ctypes
+import json
+
+import torch
+
+from . import _lib
+
+INFO_FIELDS = ("edges", "boundary_edges", "nonmanifold_edges", "misoriented_edges", "regular_edges", "verts_used", "faces_valid",
+               "adjacency")
+
+
+def _vp(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else ctypes.c_void_p(0)
+
+
+def _scratch(nbytes, dev):
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+
+
+def _faces(name, faces, num_verts):
+    if not torch.is_tensor(faces) or not faces.is_cuda:
+        raise RuntimeError(f"mesh_topology.{name} needs CUDA/HIP tensors (dg-mesh_amd has no CPU path)")
+    if faces.dtype != torch.int32:
+        raise RuntimeError(f"mesh_topology.{name}: faces must be int32, got {faces.dtype}")
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"mesh_topology.{name}: faces must be (F, 3), got {tuple(faces.shape)}")
+    if int(num_verts) < 0:
+        raise ValueError(f"mesh_topology.{name}: num_verts must be >= 0, got {num_verts}")
+    return faces.detach().contiguous()
+
+
+class EdgeTable:
+    """One mesh's edge table on the device.  The constructor runs the count call and reads the sizes back (the only read-back);
+    emit() then writes the tables asked for.  info: {field of INFO_FIELDS: int}."""
+
+    def __init__(self, name, faces, num_verts):
+        faces = _faces(name, faces, num_verts)
+        self.L = L = _lib.lib()
+        self.V, self.F, self.dev = int(num_verts), int(faces.shape[0]), faces.device
+        V, F, dev = self.V, self.F, self.dev
+        nbytes = L.dgm_mesh_edges_scratch_bytes(V, F)
+        if nbytes == 0:
+            raise ValueError(f"mesh_topology.{name}: a mesh of {V} vertices and {F} faces is over the supported 2^28 faces")
+        self.scratch = _scratch(nbytes, dev)
+        self.adj_offset = torch.empty(V + 1, dtype=torch.int32, device=dev)
+        self.vert_flag = torch.empty(V, dtype=torch.uint8, device=dev)
+        info = torch.empty(len(INFO_FIELDS), dtype=torch.int32, device=dev)
+        with _lib.device_guard(dev):
+            _lib.check(L.dgm_mesh_edges_count(V, F, _vp(faces), _vp(self.scratch), _vp(self.adj_offset), _vp(self.vert_flag), _vp(info),
+                                              _lib.stream_ptr()))
+            self.info = dict(zip(INFO_FIELDS, info.tolist()))  # the one host synchronisation: the sizes
+        self.E = self.info["edges"]
+
+    def emit(self, edges=True, faces=False, adjacency=False, kind=False):
+        """{"edges", "edge_faces", "edge_count", "adj", "adj_kind"}: the tables asked for, None for the others."""
+        E, dev = self.E, self.dev
+        new = lambda want, *shape, dtype=torch.int32: torch.empty(shape, dtype=dtype, device=dev) if want else None
+        out = {"edges": new(edges, E, 2), "edge_faces": new(faces, E, 2), "edge_count": new(faces, E, 2), "adj": new(adjacency, 2 * E),
+               "adj_kind": new(kind, 2 * E, dtype=torch.uint8)}
+        with _lib.device_guard(dev):
+            _lib.check(self.L.dgm_mesh_edges_emit(self.V, self.F, _vp(self.scratch), E, _vp(self.adj_offset), _vp(out["adj"]),
+                                                  _vp(out["adj_kind"]), _vp(out["edges"]), _vp(out["edge_faces"]), _vp(out["edge_count"]),
+                                                  _lib.stream_ptr()))
+        return out
+
+
+def mesh_edges(faces, num_verts, return_faces=False, return_adjacency=False):
+    """edges (E, 2) int32 of the module docstring; with return_faces also edge_faces and edge_count, with return_adjacency at the end
+    the pair (adj_offset, adj): a tuple in that order when anything is added."""
+    table = EdgeTable("mesh_edges", faces, num_verts)
+    t = table.emit(edges=True, faces=return_faces, adjacency=return_adjacency)
+    out = (t["edges"],)
+    if return_faces:
+        out += (t["edge_faces"], t["edge_count"])
+    if return_adjacency:
+        out += ((table.adj_offset, t["adj"]),)
+    return out if len(out) > 1 else out[0]
+
+
+def vertex_flags(faces, num_verts):
+    """vert_flag (num_verts,) uint8: bit 0 used, bit 1 on a boundary edge, bit 2 on a non-manifold or misoriented edge."""
+    return EdgeTable("vertex_flags", faces, num_verts).vert_flag
+
+
+def _verts(name, verts, dev):
+    if not torch.is_tensor(verts) or not verts.is_cuda:
+        raise RuntimeError(f"mesh_topology.{name} needs CUDA/HIP tensors (dg-mesh_amd has no CPU path)")
+    if verts.dtype != torch.float32:
+        raise RuntimeError(f"mesh_topology.{name}: verts must be float32, got {verts.dtype}")
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError(f"mesh_topology.{name}: verts must be (V, 3), got {tuple(verts.shape)}")
+    if verts.device != dev:
+        raise ValueError(f"mesh_topology.{name}: verts on {verts.device}, faces on {dev}")
+    return verts.detach().contiguous()
+
+
+def topology_report(verts, faces):
+    """{"verts", "faces": the sizes given; "verts_used", "faces_valid", "edges", "boundary_edges", "nonmanifold_edges",
+    "misoriented_edges"; "components": those of mesh_clean.connected_components that have a used vertex (faces with an index out of
+    range are left out before); "euler" = verts_used - edges + faces_valid; "watertight": the three bad-edge counts are 0 and
+    faces_valid > 0; "genus" = components - euler / 2 when watertight, else None; "edge_length": {"min", "mean", "max"} over the
+    edges, fp32 torch ops on the device, None each without an edge}."""
+    from . import mesh_clean
+    if not torch.is_tensor(faces) or not faces.is_cuda:
+        raise RuntimeError("mesh_topology.topology_report needs CUDA/HIP tensors (dg-mesh_amd has no CPU path)")
+    verts = _verts("topology_report", verts, faces.device)
+    V = int(verts.shape[0])
+    table = EdgeTable("topology_report", faces, V)
+    info = table.info
+    rep = {"verts": V, "faces": table.F}
+    rep.update({k: info[k] for k in ("verts_used", "faces_valid", "edges", "boundary_edges", "nonmanifold_edges", "misoriented_edges")})
+    faces = faces.detach()
+    inside = ((faces >= 0) & (faces < V)).all(dim=1)
+    rep["components"] = 0
+    if rep["faces_valid"] > 0:
+        labels = mesh_clean.connected_components(faces[inside].contiguous(), V)
+        roots = labels == torch.arange(V, dtype=torch.int32, device=labels.device)
+        rep["components"] = int((roots & ((table.vert_flag & 1) != 0)).sum())
+    rep["euler"] = rep["verts_used"] - rep["edges"] + rep["faces_valid"]
+    rep["watertight"] = (rep["boundary_edges"] == 0 and rep["nonmanifold_edges"] == 0 and rep["misoriented_edges"] == 0
+                         and rep["faces_valid"] > 0)
+    rep["genus"] = None
+    if rep["watertight"]:
+        rep["genus"] = rep["components"] - rep["euler"] // 2 if rep["euler"] % 2 == 0 else rep["components"] - rep["euler"] / 2
+    rep["edge_length"] = {"min": None, "mean": None, "max": None}
+    if table.E > 0:
+        e = table.emit(edges=True)["edges"].long()
+        length = (verts[e[:, 0]] - verts[e[:, 1]]).norm(dim=1)
+        lo, mean, hi = torch.stack((length.min(), length.mean(), length.max())).tolist()
+        rep["edge_length"] = {"min": lo, "mean": mean, "max": hi}
+    return rep
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(prog="python -m dgmesh_amd.mesh_topology",
+                                 description="Print the topology report of triangle-mesh PLY files, one JSON object per file.")
+    ap.add_argument("meshes", nargs="+", help="triangle-mesh PLY files (ply_io's format)")
+    return ap
+
+
+def main(argv=None):
+    from .ply_io import read_mesh_ply
+    args = build_parser().parse_args(argv)
+    dev = torch.device("cuda")
+    for path in args.meshes:
+        verts, faces = read_mesh_ply(path)[:2]
+        rep = topology_report(torch.from_numpy(verts).to(dev), torch.from_numpy(faces).to(dev))
+        print(json.dumps({"path": path, **rep}))
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

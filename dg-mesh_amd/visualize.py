@@ -380,15 +380,17 @@ def render_trajectory(gaussians, deform, deform_back, template_cam, *, mesh, def
 
 
 @torch.no_grad()
-def export_dynamic_mesh(gaussians, deform, deform_back, mesh, out_dir, frames=200, deform_normal=None, clean=None, simplify=None):
+def export_dynamic_mesh(gaussians, deform, deform_back, mesh, out_dir, frames=200, deform_normal=None, clean=None, simplify=None, smooth=None):
     """The dynamic-mesh sequence of R/train.py:389-423: dynamic_mesh/frame_{i}.ply under out_dir for t = i / frames, i < frames,
     with vertex colours (ply_io.write_mesh_ply).  Colours are written as clamp(c, 0, 1) * 255 truncated, as testing() writes them;
     the reference's astype(np.uint8) of the unscaled [0, 1] colours at this place is a bug (every channel becomes 0 or 1).
     clean: None, or a mesh_clean.CleanSpec (or a dict of its fields): each written mesh loses the components that fail it
     (mesh_clean.clean_mesh; the colours follow their vertices).  simplify: None, or a mesh_simplify.SimplifySpec (or a dict of its
     fields): each written mesh is then decimated by quadric vertex clustering, after `clean`; a new vertex takes the colour of its
-    cluster's representative.  -> the list of paths."""
-    from . import mesh_clean, mesh_simplify
+    cluster's representative.  smooth: None, or a mesh_smooth.SmoothSpec (or a dict of its fields): each written mesh is smoothed
+    (Taubin or Laplacian, mesh_smooth.smooth_mesh) after `clean` and BEFORE `simplify` -- denoised first, decimated after; faces and
+    colours are untouched by it.  -> the list of paths."""
+    from . import mesh_clean, mesh_simplify, mesh_smooth
     from .evaluate import mesh_and_colors
     from .ply_io import write_mesh_ply
     who = "export_dynamic_mesh"
@@ -405,6 +407,7 @@ def export_dynamic_mesh(gaussians, deform, deform_back, mesh, out_dir, frames=20
         fid = torch.tensor([i / n], dtype=torch.float32, device=dev)
         _, d_xyz, d_normal = _deformations(gaussians, deform, deform_normal, fid)
         verts, faces, vtx_color = mesh_clean.apply(clean, *mesh_and_colors(mesh, gaussians, deform_back, d_xyz, d_normal, fid, who=who))
+        verts, faces, vtx_color = mesh_smooth.apply(smooth, verts, faces, vtx_color)
         verts, faces, vtx_color = mesh_simplify.apply(simplify, verts, faces, vtx_color)
         paths.append(os.path.join(out_dir, "dynamic_mesh", f"frame_{i}.ply"))
         write_mesh_ply(paths[-1], verts, faces, vertex_colors=vtx_color)

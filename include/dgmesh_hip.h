@@ -774,6 +774,48 @@ int dgm_mesh_simplify_place(int V, int F, const float* verts, const int* faces, 
                             int ny, int nz, float h, double regularization, char* scratch, float* placed, void* stream);
 int dgm_mesh_simplify_vert_map(int V, int F, int Vn, const int* vert_index, char* scratch, int* vert_map, void* stream);
 
+/* ---- the edge table of a mesh, its topology classes, Taubin / Laplacian smoothing (csrc/mesh_edges.hip) -------------------------------
+ * Replaces compute_edges and compute_edge_to_face_mapping (dgmesh/nvdiffrast_utils/mesh.py:97-149, torch.unique) and gives what a
+ * host mesh library is otherwise asked for: is the mesh closed, where is its rim, lambda | mu smoothing (Taubin 1995).  faces (F, 3)
+ * int32, verts (V, 3) fp32; every buffer is device memory, nothing is allocated and nothing is read back.  Definitions:
+ *   VALID face: indices in [0, V) (range-checked before any use) and pairwise different (mesh_clean's definition; coordinates play
+ *       no part in topology).  A valid face (a, b, c) TRAVERSES the directed half-edges a->b, b->c and c->a.  A vertex is USED when a
+ *       valid face uses it.
+ *   ADJACENCY: adj_offset (V + 1) and adj (2 E) int32: adj[adj_offset[v] .. adj_offset[v + 1]) = the distinct vertices that share
+ *       a valid face's side with v, ascending; empty for an unused vertex; adj_offset[V] = 2 E.
+ *   EDGES: edges (E, 2) int32 = the distinct unordered sides {u, v} of the valid faces as u < v, in lexicographic order: on a mesh
+ *       of valid faces what compute_edges returns (torch.unique(dim=0) order).  edge_count (E, 2) int32 = the valid faces that traverse
+ *       u->v (column 0) and v->u (column 1); edge_faces (E, 2) int32 = the smallest index among those faces per column, -1 for none
+ *       (the reference's table writes 0 there and keeps an arbitrary face where several compete).
+ *   CLASSES of an edge from its counts: BOUNDARY, they sum to 1; MISORIENTED, (2, 0) or (0, 2); NON-MANIFOLD, the sum is >= 3;
+ *       REGULAR, (1, 1).  adj_kind (2 E) bytes = the class of the edge to each adjacency entry: 0 regular, 1 boundary,
+ *       2 non-manifold, 3 misoriented.  vert_flag (V) bytes: bit 0 used, bit 1 on a boundary edge, bit 2 on a non-manifold or
+ *       misoriented edge.
+ *   SMOOTHING STEP with factor f on vertex i with neighbour set N: m = (the sum of in[n], n in N, in fp64, starting from 0, in
+ *       ascending n) / (double)|N|, out[i] = (float)(x + f (m - x)) with x = (double)in[i], per coordinate, no contraction: one
+ *       rounding to fp32.  Copied unchanged: a vertex with a non-finite coordinate, one with an empty N, and with boundary = 0 (FIXED)
+ *       a vertex with flag bit 1.  boundary = 1 (CURVE): for a vertex with flag bit 1, N is restricted to the neighbours it is joined
+ *       to by a boundary edge; boundary = 2 (FREE): no distinction.  A non-finite NEIGHBOUR is not left out: its vertex's sum, and
+ *       with it that output row, becomes non-finite by the rules of IEEE arithmetic.
+ * Every output is bit-reproducible: integer atomics hand out counts and places only, every list is then ordered by ranking, no
+ * float is added by an atomic.  F <= 2^28.
+ *   dgm_mesh_edges_count: builds the sorted lists in scratch; adj_offset (V + 1), vert_flag (V) and info (8 ints) = E, boundary edges,
+ *       non-manifold edges, misoriented edges, regular edges, used vertices, valid faces, 2 E.  The caller reads info back to size
+ *       the outputs of the emit call.  scratch: dgm_mesh_edges_scratch_bytes(V, F) bytes (0 for a negative or unsupported size),
+ *       handed on to the emit call unchanged.
+ *   dgm_mesh_edges_emit: after _count on the same scratch and adj_offset, E = info[0]; writes adj (2 E), adj_kind (2 E), edges,
+ *       edge_faces and edge_count ((E, 2) each); any of them may be NULL and is then left out; nothing is written at or behind E
+ *       rows or 2 E entries.
+ *   dgm_mesh_smooth_step: one step verts_in -> verts_out (different buffers), A = the entries of adj; adj_kind is read with
+ *       boundary = 1 only.  An adjacency offset outside [0, A] or a neighbour outside [0, V) copies its vertex unchanged.  A Taubin
+ *       iteration is two calls, f = lambda and then f = mu. */
+size_t dgm_mesh_edges_scratch_bytes(int V, int F);
+int dgm_mesh_edges_count(int V, int F, const int* faces, char* scratch, int* adj_offset, unsigned char* vert_flag, int* info, void* stream);
+int dgm_mesh_edges_emit(int V, int F, char* scratch, int E, const int* adj_offset, int* adj, unsigned char* adj_kind, int* edges,
+                        int* edge_faces, int* edge_count, void* stream);
+int dgm_mesh_smooth_step(int V, int A, const float* verts_in, const int* adj_offset, const int* adj, const unsigned char* adj_kind,
+                         const unsigned char* vert_flag, double factor, int boundary, float* verts_out, void* stream);
+
 /* ---- closest point on a triangle mesh, interpolation, correspondence colours (csrc/surface.hip) -------------------------------------
  * What carries a surface point from one frame's mesh onto another's (correspondence.py).  verts (V, 3) fp32, faces (F, 3) int32;
  * every buffer is device memory, nothing is allocated and nothing is read back.
