@@ -190,6 +190,41 @@ def eval_distance(gt_verts, gt_faces, eval_verts, eval_faces, rotate=None, cam_o
     return chamfer, emd_cd(gs[None], es[None])["EMD"]
 
 
+def _mesh_pairs(who, gt_mesh_path, eval_mesh_path, eval_model_type):
+    """What evaluation and evaluation_iou share before the device is touched: -> ([(gt file, predicted file)], camera_origin or
+    None, the current device); the ValueErrors are those evaluation documents."""
+    if eval_model_type not in ROTATIONS:
+        raise ValueError(f"mesh_eval.{who}: eval_model_type {eval_model_type!r} not supported (one of {sorted(ROTATIONS)})")
+    gt_list = sorted(glob.glob(os.path.join(gt_mesh_path, "*.obj")))
+    eval_list = sorted(glob.glob(os.path.join(eval_mesh_path, "*.ply")))
+    if len(gt_list) != len(eval_list):
+        raise ValueError(f"mesh_eval.{who}: {len(gt_list)} ground-truth meshes in {gt_mesh_path} but {len(eval_list)} predicted "
+                         f"meshes in {eval_mesh_path}")
+    if not gt_list:
+        raise ValueError(f"mesh_eval.{who}: no *.obj in {gt_mesh_path}")
+    cam_origin = None
+    json_path = os.path.join(os.path.dirname(os.path.abspath(gt_mesh_path)), "transforms_train.json")
+    if os.path.exists(json_path):
+        with open(json_path, "r") as fh:
+            cam_origin = json.load(fh).get("camera_origin")
+    return list(zip(gt_list, eval_list)), cam_origin, torch.device("cuda", torch.cuda.current_device())
+
+
+def _load_pair(who, gt_file, eval_file, clean, dev):
+    """-> (gt verts, gt faces, predicted verts, predicted faces) on the device, the prediction cleaned when `clean` says so."""
+    from . import mesh_clean
+    from .ply_io import read_mesh_ply
+    gv, gf = read_mesh_obj(gt_file)
+    ev, ef = read_mesh_ply(eval_file)
+    to = lambda a: torch.from_numpy(a).to(dev)
+    ev, ef = to(ev), to(ef)
+    if clean is not None:
+        ev, ef = mesh_clean.apply(clean, ev, ef)
+        if ev.shape[0] == 0:
+            raise ValueError(f"mesh_eval.{who}: nothing of {eval_file} is left after cleaning ({clean.describe()})")
+    return to(gv), to(gf), ev, ef
+
+
 def evaluation(gt_mesh_path, eval_mesh_path, eval_model_type, emd_sample=8192, seed=0, clean=None):
     """evaluation of R/mesh_evaluation.py:98-178: the sorted *.obj of gt_mesh_path against the sorted *.ply of eval_mesh_path,
     -> (avg_cd, cd_list, avg_emd, emd_list) as Python floats.  camera_origin is read from ../transforms_train.json of the ground
@@ -199,40 +234,40 @@ def evaluation(gt_mesh_path, eval_mesh_path, eval_model_type, emd_sample=8192, s
     PREDICTED mesh loses the components that fail it before it is scored (mesh_clean.clean_mesh, which reads the output sizes back
     per mesh); a prediction of which nothing is left raises ValueError."""
     from . import mesh_clean
-    from .ply_io import read_mesh_ply
     clean = mesh_clean.as_spec(clean)
-    if eval_model_type not in ROTATIONS:
-        raise ValueError(f"mesh_eval.evaluation: eval_model_type {eval_model_type!r} not supported (one of {sorted(ROTATIONS)})")
-    gt_list = sorted(glob.glob(os.path.join(gt_mesh_path, "*.obj")))
-    eval_list = sorted(glob.glob(os.path.join(eval_mesh_path, "*.ply")))
-    if len(gt_list) != len(eval_list):
-        raise ValueError(f"mesh_eval.evaluation: {len(gt_list)} ground-truth meshes in {gt_mesh_path} but {len(eval_list)} predicted "
-                         f"meshes in {eval_mesh_path}")
-    if not gt_list:
-        raise ValueError(f"mesh_eval.evaluation: no *.obj in {gt_mesh_path}")
-    cam_origin = None
-    json_path = os.path.join(os.path.dirname(os.path.abspath(gt_mesh_path)), "transforms_train.json")
-    if os.path.exists(json_path):
-        with open(json_path, "r") as fh:
-            cam_origin = json.load(fh).get("camera_origin")
-    dev = torch.device("cuda", torch.cuda.current_device())
+    pairs, cam_origin, dev = _mesh_pairs("evaluation", gt_mesh_path, eval_mesh_path, eval_model_type)
     generator = torch.Generator(device=dev).manual_seed(int(seed))
-    table = torch.empty((len(gt_list), 2), dtype=torch.float64, device=dev)
-    for i, (gt_file, eval_file) in enumerate(zip(gt_list, eval_list)):
-        gv, gf = read_mesh_obj(gt_file)
-        ev, ef = read_mesh_ply(eval_file)
-        to = lambda a: torch.from_numpy(a).to(dev)
-        ev, ef = to(ev), to(ef)
-        if clean is not None:
-            ev, ef = mesh_clean.apply(clean, ev, ef)
-            if ev.shape[0] == 0:
-                raise ValueError(f"mesh_eval.evaluation: nothing of {eval_file} is left after cleaning ({clean.describe()})")
-        cd, emd = eval_distance(to(gv), to(gf), ev, ef, rotate=ROTATIONS[eval_model_type], cam_origin=cam_origin,
+    table = torch.empty((len(pairs), 2), dtype=torch.float64, device=dev)
+    for i, (gt_file, eval_file) in enumerate(pairs):
+        gv, gf, ev, ef = _load_pair("evaluation", gt_file, eval_file, clean, dev)
+        cd, emd = eval_distance(gv, gf, ev, ef, rotate=ROTATIONS[eval_model_type], cam_origin=cam_origin,
                                 emd_sample=emd_sample, generator=generator)
         table[i, 0], table[i, 1] = cd, emd
     host = table.cpu().numpy()  # the one read-back
     cd_list, emd_list = [float(v) for v in host[:, 0]], [float(v) for v in host[:, 1]]
     return float(np.mean(cd_list)), cd_list, float(np.mean(emd_list)), emd_list
+
+
+def evaluation_iou(gt_mesh_path, eval_mesh_path, eval_model_type, n_points=100000, seed=0, clean=None):
+    """The volumetric IoU (mesh_inside.volume_iou, absolute=True: either winding counts as inside) of every predicted mesh against
+    its ground truth, -> (avg_iou, iou_list) as Python floats.  The folders, the rotation of the predicted vertices, the
+    camera_origin shift of the ground truth, `clean` and the ValueErrors are evaluation()'s; the n_points samples of every pair come
+    from one generator seeded with `seed`.  Cost: n_points x (faces of both meshes) pairs per item.  The results stay on the device
+    until one read-back after the last mesh.  A pair neither of whose meshes encloses a sample gives NaN."""
+    from . import mesh_clean, mesh_inside
+    clean = mesh_clean.as_spec(clean)
+    pairs, cam_origin, dev = _mesh_pairs("evaluation_iou", gt_mesh_path, eval_mesh_path, eval_model_type)
+    generator = torch.Generator(device=dev).manual_seed(int(seed))
+    rot = torch.as_tensor(np.asarray(ROTATIONS[eval_model_type], np.float32), device=dev)
+    table = torch.empty(len(pairs), dtype=torch.float64, device=dev)
+    for i, (gt_file, eval_file) in enumerate(pairs):
+        gv, gf, ev, ef = _load_pair("evaluation_iou", gt_file, eval_file, clean, dev)
+        if cam_origin is not None:
+            gv = gv - torch.tensor(_CAM_ORIGIN_MATRIX @ np.asarray(cam_origin, np.float64).reshape(3), dtype=torch.float32, device=dev)
+        ev = (rot @ ev.T).T.contiguous()
+        table[i] = mesh_inside.volume_iou(gv, gf, ev, ef, n_points=n_points, generator=generator, absolute=True)["iou"]
+    iou_list = [float(v) for v in table.cpu().numpy()]  # the one read-back
+    return float(np.mean(iou_list)), iou_list
 
 
 def build_parser():
@@ -241,6 +276,8 @@ def build_parser():
     ap.add_argument("--eval_type", required=True, choices=sorted(ROTATIONS))
     ap.add_argument("--emd_sample", type=int, default=8192)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--iou", type=int, nargs="?", const=100000, default=None, metavar="N",
+                    help="also score the volumetric IoU of every pair, on N uniform samples of the union bounding box (default 100000)")
     ap.add_argument("--largest_component", action="store_true", help="score only the largest component of each predicted mesh")
     ap.add_argument("--min_component_faces", type=int, default=0, metavar="N", help="drop predicted components with fewer faces")
     ap.add_argument("--min_component_diameter", type=float, default=0.0, metavar="FRAC",
@@ -279,6 +316,11 @@ def main(argv=None):
         print(f"Item {i}: CD {cd:.10f}, EMD {emd:.4f}")
     print(f"Average Chamfer distance: {avg_cd:.4f}")
     print(f"Average EMD: {avg_emd:.4f}")
+    if args.iou is not None:
+        avg_iou, iou_list = evaluation_iou(gt_path, pred_path, args.eval_type, n_points=args.iou, seed=args.seed, clean=clean)
+        for i, iou in enumerate(iou_list):
+            print(f"Item {i}: IoU {iou:.6f}")
+        print(f"Average volume IoU: {avg_iou:.6f}")
     os.makedirs(log_folder, exist_ok=True)
     out = os.path.join(log_folder, "eval_results.txt")
     with open(out, "w") as fh:
@@ -286,6 +328,10 @@ def main(argv=None):
         fh.write(f"Pred source: {pred_path}\n")
         fh.write(f"Average Chamfer distance: {avg_cd:.10f}\n")
         fh.write(f"Average EMD: {avg_emd:.4f}\n")
+        if args.iou is not None:
+            for i, iou in enumerate(iou_list):
+                fh.write(f"Item {i}: IoU {iou:.6f}\n")
+            fh.write(f"Average volume IoU: {avg_iou:.6f}\n")
         if clean is not None:
             fh.write(f"Predicted meshes cleaned: {clean.describe()}\n")
     return out

@@ -816,6 +816,28 @@ int dgm_mesh_edges_emit(int V, int F, char* scratch, int E, const int* adj_offse
 int dgm_mesh_smooth_step(int V, int A, const float* verts_in, const int* adj_offset, const int* adj, const unsigned char* adj_kind,
                          const unsigned char* vert_flag, double factor, int boundary, float* verts_out, void* stream);
 
+/* ---- inside / outside: the generalised winding number of query points (csrc/mesh_inside.hip) ------------------------------------------
+ * What answers whether a point is inside a mesh (mesh_inside.py: contains, signed_distance, occupancy_grid, volume_iou).  points
+ * (N, 3), verts (V, 3) fp32, faces (F, 3) int32; every buffer is device memory, nothing is allocated and nothing is read back.
+ * WINDING NUMBER.  For query p and a face with corners v0, v1, v2, all in fp32 without contraction, a = v0 - p, b = v1 - p, c = v2 - p:
+ *       det = a . (b x c),  den = |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|,  omega = 2 atan2(det, den)  (van Oosterom and Strackee),
+ *       w(p) = (1 / 4 pi) sum over the faces of omega -- the order of every operation is written out at the head of
+ *       csrc/mesh_inside.hip; the lengths come from the hardware's square root (within 1 ulp), atan2 is the device library's atan2f.  1 inside a closed mesh wound outwards, 0 outside, -1 inside one wound inwards; the sum over nested or
+ *       overlapping shells; a fraction near an open rim.  A face adds exactly 0 when one of its indices lies outside [0, V) (checked
+ *       before any use), when a corner coordinate is not finite, or when det is exactly 0 or not finite: a face with b = c or three
+ *       equal corners, and the arbitrary +-2 pi of atan2(+-0, negative) for a query in a face's plane (another face without area has
+ *       a det of rounding noise and adds about as little).  A query with a non-finite coordinate gets NaN.  On
+ *       the surface itself the value is unspecified but finite.  V = 0 or F = 0: w = 0.  N = 0: nothing is done.
+ * SUMMATION ORDER.  Faces in index order; omega is added in fp32, from 0, within a chunk of 256 faces; the chunk sums are added in
+ *       fp64, in order, within a slice of 64 chunks (16384 faces); the slice sums are added in fp64, in order; w = (float)(sum / (4 pi)),
+ *       one rounding.  The structure is a function of F alone: a query's w is the same bit pattern whether it is asked alone or
+ *       among others, and from run to run; a caller may split N into batches freely.  No atomics.
+ *   dgm_wind_scratch_bytes: N * ceil(F / 16384) * 8, the fp64 slice sums (0 for a negative size).
+ *   dgm_wind_number: w (N) fp32.  scratch: dgm_wind_scratch_bytes(N, F) bytes, 8-byte aligned, contents irrelevant; not touched (and
+ *       may be NULL) when F <= 16384.  N x slices beyond 2^31 - 1 workgroups of 256 queries is refused: split N. */
+size_t dgm_wind_scratch_bytes(int N, int F);
+int dgm_wind_number(int N, int V, int F, const float* points, const float* verts, const int* faces, char* scratch, float* w, void* stream);
+
 /* ---- closest point on a triangle mesh, interpolation, correspondence colours (csrc/surface.hip) -------------------------------------
  * What carries a surface point from one frame's mesh onto another's (correspondence.py).  verts (V, 3) fp32, faces (F, 3) int32;
  * every buffer is device memory, nothing is allocated and nothing is read back.
