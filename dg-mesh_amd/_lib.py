@@ -114,6 +114,10 @@ SYMBOLS = {
     "dgm_tri_aa_scratch_bytes": (_c.c_size_t, [_i]),
     "dgm_tri_antialias_forward": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dgm_tri_antialias_backward": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_tri_texture_forward": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "dgm_tri_texture_backward": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_atlas_uv": (_i, [_i, _i, _i, _vp, _vp]),
+    "dgm_atlas_interpolate": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dgm_anchor_face_geometry": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dgm_anchor_nn_scratch_bytes": (_c.c_size_t, [_i, _i]),
     "dgm_anchor_nn": (_i, [_i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp]),

@@ -86,8 +86,8 @@ def _mesh_view(mesh, gaussians, deform_back, d_xyz, d_normal, cam, white_backgro
 
 @torch.no_grad()
 def testing(gaussians, deform, deform_back, cameras, *, pipe, background, mesh=None, deform_normal=None, is_6dof=False,
-            white_background=True, out_dir=None, save_meshes=False, lpips=None, clean=None, simplify=None, smooth=None):
-    """testing() of R/train.py:559-761 without the image / glb files.  Per camera: deform.step at the camera's
+            white_background=True, out_dir=None, save_meshes=False, lpips=None, clean=None, simplify=None, smooth=None, save_glb=False):
+    """testing() of R/train.py:559-761 without the image files.  Per camera: deform.step at the camera's
     fid, scene.render clamped to [0, 1]; with `mesh` (a trainer.MeshPhase that has a DPSR module) also mesh.psr -> mesh.surface ->
     deform_back + mesh.appearance on the vertices -> mesh_raster.render_mesh (deform_normal: the network whose first output is added
     to the normals; None = mesh.deform_normal).  One image_metrics call per view scores both images against cam.original_image
@@ -105,6 +105,8 @@ def testing(gaussians, deform, deform_back, cameras, *, pipe, background, mesh=N
     mesh_simplify.SimplifySpec (or a dict of its fields): the WRITTEN mesh only is decimated by quadric vertex clustering, after
     `clean`, the colours taken at the representatives.  smooth: None, or a mesh_smooth.SmoothSpec (or a dict of its fields): the
     WRITTEN mesh only is smoothed (mesh_smooth.smooth_mesh), after `clean` and BEFORE `simplify` -- denoised first, decimated after.
+    save_glb: also writes the reference's test_results/dynamic_glb/frame_{idx}.glb (R/train.py:740), the same written mesh with its
+    vertex colours as binary glTF (glb_io.write_mesh_glb); needs mesh and out_dir.
 
     lpips: None, or {"alex": lpips.LPIPS, "vgg": lpips.LPIPS} with either key optional.  Each network then scores both images of a
     view against the target in one call (the target's features are computed once) into a second device-side table that the same
@@ -116,6 +118,8 @@ def testing(gaussians, deform, deform_back, cameras, *, pipe, background, mesh=N
         raise RuntimeError("testing: mesh must be a MeshPhase with a DPSR module")
     if save_meshes and (mesh is None or out_dir is None):
         raise ValueError("testing: save_meshes needs mesh and out_dir")
+    if save_glb and (mesh is None or out_dir is None):
+        raise ValueError("testing: save_glb needs mesh and out_dir")
     cameras = list(cameras)
     if not cameras:
         raise ValueError("testing: no cameras")
@@ -154,13 +158,17 @@ def testing(gaussians, deform, deform_back, cameras, *, pipe, background, mesh=N
         _metrics_into(images, gt, table[idx, :images.shape[0]], 1.0, 5 if ms else 1)
         for j, net in enumerate(nets):
             lpips[net]._into(*LP._checked(images, gt, net), lp_table[idx, j, :images.shape[0]])
-        if save_meshes:
+        if save_meshes or save_glb:
             from . import mesh_clean, mesh_simplify, mesh_smooth
-            from .ply_io import write_mesh_ply
             w_verts, w_faces, w_color = mesh_clean.apply(clean, verts, faces, vtx_color)
             w_verts, w_faces, w_color = mesh_smooth.apply(smooth, w_verts, w_faces, w_color)
             w_verts, w_faces, w_color = mesh_simplify.apply(simplify, w_verts, w_faces, w_color)
-            write_mesh_ply(os.path.join(saving_path, "dynamic_mesh", f"frame_{idx}.ply"), w_verts, w_faces, vertex_colors=w_color)
+            if save_meshes:
+                from .ply_io import write_mesh_ply
+                write_mesh_ply(os.path.join(saving_path, "dynamic_mesh", f"frame_{idx}.ply"), w_verts, w_faces, vertex_colors=w_color)
+            if save_glb:
+                from .glb_io import write_mesh_glb
+                write_mesh_glb(os.path.join(saving_path, "dynamic_glb", f"frame_{idx}.glb"), w_verts, w_faces, vertex_colors=w_color)
     torch.cuda.synchronize(dev)
     total = time.perf_counter() - t0
     both = table.flatten() if lp_table is None else torch.cat((table.flatten(), lp_table.flatten()))

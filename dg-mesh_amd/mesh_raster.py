@@ -4,6 +4,7 @@ R/utils/renderer.py:33-121; R/ = the reference's dgmesh/):
     rasterize(glctx, pos, tri, resolution)   -> (rast (1, H, W, 4), None)
     interpolate(attr, rast, tri)             -> (out (1, H, W, C), None)
     antialias(color, rast, pos, tri)         -> out (1, H, W, C)
+    texture(tex, uv, ...)                    -> out (1, H, W, C)
 
 so a caller of nvdiffrast.torch can switch imports.  `glctx` is accepted and ignored (None is fine).  The passes are HIP kernels
 of libdgmesh_hip (csrc/mesh_raster.hip) behind torch.autograd.Function.  float32 / int32, CUDA/HIP tensors only, batch size 1 --
@@ -33,8 +34,15 @@ that costs nothing):
     axis-aligned straight edge; it reproduces coverage along each row and column.  The only path from a mask loss to the
     geometry.  The edge topology is rebuilt on the device every call (DiffMC's faces change every step);
   * float atomics only in the backward scatters (dpos, dattr): those agree to rounding run to run; every forward output is
-    bit-identical run to run.
-Not provided: MSAA, texture, rast_db, depth peeling, range mode, batches larger than 1.
+    bit-identical run to run;
+  * texture: tex (1, Ht, Wt, C), uv (1, ..., 2); texel (i, j) is centred at u = (i + .5) / Wt, v = (j + .5) / Ht and row 0 of memory is
+    at v = 0 (nvdiffrast's documented convention).  filter_mode "linear" (= "auto"): bilinear over the four texels around
+    (u Wt - .5, v Ht - .5); "nearest": texel (floor(u Wt), floor(v Ht)).  boundary_mode "wrap": indices modulo the size; "clamp":
+    indices clamped; "zero": texels outside count as 0.  A non-finite uv gives zeros and no gradient; a finite uv of any magnitude
+    reads nothing outside tex.  Gradients to tex (fp32 atomics, as dattr) and to uv (zero for "nearest").  csrc/mesh_texture.hip
+    states the operation order.
+Not provided: MSAA, mip-maps (uv_da, mip_level_bias, mip, max_mip_level, the linear-mipmap filters: they need rast_db), cube maps,
+rast_db, depth peeling, range mode, batches larger than 1.
 """
 import ctypes
 
@@ -168,6 +176,38 @@ class _Antialias(torch.autograd.Function):
         return dcolor, None, dpos, None
 
 
+FILTER_MODES = ("nearest", "linear")          # the int of the C ABI is the index
+BOUNDARY_MODES = ("wrap", "clamp", "zero")    # likewise
+
+
+class _Texture(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tex, uv, filt, boundary):
+        Ht, Wt, C = int(tex.shape[1]), int(tex.shape[2]), int(tex.shape[3])
+        n = uv.numel() // 2
+        out = torch.empty(tuple(uv.shape[:-1]) + (C,), dtype=torch.float32, device=tex.device)
+        with _lib.device_guard(tex.device):
+            _lib.check(_lib.lib().dgm_tri_texture_forward(n, Ht, Wt, C, filt, boundary, _vp(tex), _vp(uv), _vp(out), _st()))
+        ctx.save_for_backward(tex, uv)
+        ctx.modes = (filt, boundary)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        tex, uv = ctx.saved_tensors
+        filt, boundary = ctx.modes
+        Ht, Wt, C = int(tex.shape[1]), int(tex.shape[2]), int(tex.shape[3])
+        n = uv.numel() // 2
+        dout = dout.contiguous().float()
+        dtex = torch.empty_like(tex)
+        duv = torch.empty_like(uv)
+        with _lib.device_guard(tex.device):
+            _lib.check(_lib.lib().dgm_tri_texture_backward(n, Ht, Wt, C, filt, boundary, _vp(tex), _vp(uv), _vp(dout), _vp(dtex), _vp(duv),
+                                                           _st()))
+        return dtex, duv, None, None
+
+
 def rasterize(glctx, pos, tri, resolution, ranges=None, grad_db=True):
     """nvdiffrast.torch.rasterize for batch size 1: (rast (1, H, W, 4) = (u, v, z/w, id + 1), None).  `glctx` and `grad_db` are
     ignored; `ranges` (range mode) is not supported."""
@@ -212,6 +252,37 @@ def antialias(color, rast, pos, tri, topology_hash=None, pos_gradient_boost=1.0)
     return _Antialias.apply(color, rast, pos, tri)
 
 
+def texture(tex, uv, uv_da=None, mip_level_bias=None, mip=None, filter_mode="auto", boundary_mode="wrap", max_mip_level=None):
+    """nvdiffrast.torch.texture for batch size 1 without mip-maps: tex (1, Ht, Wt, C), uv (1, H, W, 2) (or any (1, ..., 2)) ->
+    out (1, H, W, C) (module docstring for the conventions).  filter_mode: "auto" (= "linear"), "linear" or "nearest";
+    boundary_mode: "wrap", "clamp" or "zero".  Mip-maps (`uv_da`, `mip_level_bias`, `mip`, `max_mip_level`, the "linear-mipmap-*"
+    filters) and cube maps are not supported."""
+    if uv_da is not None or mip_level_bias is not None or mip is not None or max_mip_level is not None:
+        raise RuntimeError("texture: mip-maps (uv_da, mip_level_bias, mip, max_mip_level) are not supported")
+    if isinstance(filter_mode, str) and filter_mode.startswith("linear-mipmap"):
+        raise RuntimeError(f"texture: mip-maps (filter_mode {filter_mode!r}) are not supported")
+    if boundary_mode == "cube":
+        raise RuntimeError("texture: cube maps (boundary_mode 'cube') are not supported")
+    filter_mode = "linear" if filter_mode == "auto" else filter_mode
+    if filter_mode not in FILTER_MODES:
+        raise RuntimeError(f"texture: filter_mode must be one of auto, {', '.join(FILTER_MODES)}, got {filter_mode!r}")
+    if boundary_mode not in BOUNDARY_MODES:
+        raise RuntimeError(f"texture: boundary_mode must be one of {', '.join(BOUNDARY_MODES)}, got {boundary_mode!r}")
+    _need("texture", tex, "tex", torch.float32)
+    _need("texture", uv, "uv", torch.float32)
+    if tex.dim() != 4 or tex.shape[3] < 1:
+        raise RuntimeError(f"texture: tex must be (1, Ht, Wt, C) with C >= 1, got {tuple(tex.shape)}")
+    if uv.dim() < 2 or uv.shape[-1] != 2:
+        raise RuntimeError(f"texture: uv must be (1, ..., 2), got {tuple(uv.shape)}")
+    if tex.shape[0] != 1 or uv.shape[0] != 1:
+        raise RuntimeError(f"texture: only batch size 1 is supported, got tex {tuple(tex.shape)} and uv {tuple(uv.shape)}")
+    if not (0 < tex.shape[1] <= 16384 and 0 < tex.shape[2] <= 16384):
+        raise RuntimeError(f"texture: the texture's sides must be within [1, 16384], got {tuple(tex.shape)}")
+    if uv.device != tex.device:
+        raise RuntimeError("texture: tex and uv must be on one device")
+    return _Texture.apply(tex, uv, FILTER_MODES.index(filter_mode), BOUNDARY_MODES.index(boundary_mode))
+
+
 def clip_positions(cam, verts):
     """[verts, 1] @ cam.full_proj_transform as (1, V, 4) clip-space positions (differentiable w.r.t. verts)."""
     hom = torch.cat([verts, torch.ones_like(verts[:, :1])], dim=1)
@@ -243,6 +314,37 @@ def render_mask_and_mesh(glctx, verts, faces, vtx_color, cam, resolution=None, w
     bg = 1.0 if whitebackground else 0.0
     image = torch.where(mask != 0, col[..., :3], torch.full_like(col[..., :3], bg)).clamp(0.0, 1.0)
     return mask, image.permute(2, 0, 1)
+
+
+def render_mesh_textured(glctx, verts, faces, uv, tex, cam, resolution=None, whitebackground=False, rast=None):
+    """render_mesh with the colour looked up in a texture instead of interpolated from the vertices: rasterize, interpolate of the
+    per-corner uv (F, 3, 2) (its own index array arange(3F): every face has its own three uv rows, as mesh_texture's atlas gives
+    them), texture(..., boundary_mode="clamp"), antialias, then render_mesh's background rule; (3, H, W).  tex (Ht, Wt, 3) or
+    (1, Ht, Wt, 3).  Background pixels carry colour 0 and coverage 0 into antialias, as in render_mesh."""
+    H, W = _resolution(cam, resolution)
+    pos = clip_positions(cam, verts)
+    faces = faces.contiguous()
+    F = int(faces.shape[0])
+    if tuple(uv.shape) != (F, 3, 2):
+        raise RuntimeError(f"render_mesh_textured: uv must be ({F}, 3, 2), one row per face corner, got {tuple(uv.shape)}")
+    if tex.dim() == 3:
+        tex = tex.unsqueeze(0)
+    if rast is None:
+        rast, _ = rasterize(glctx, pos, faces, (H, W))
+    else:
+        _check_rast("render_mesh_textured", rast, pos.device)
+        if tuple(rast.shape[1:3]) != (H, W):
+            raise RuntimeError(f"render_mesh_textured: rast {tuple(rast.shape)} does not match the resolution {(H, W)}")
+    corner = torch.arange(3 * F, dtype=torch.int32, device=faces.device).reshape(F, 3)
+    uv_px, _ = interpolate(uv.reshape(3 * F, 2).contiguous(), rast, corner)
+    rgb = texture(tex.contiguous(), uv_px, filter_mode="linear", boundary_mode="clamp")
+    covered = (rast[..., 3:4] > 0).to(rgb.dtype)
+    col = (torch.cat([rgb, torch.ones_like(rgb[..., :1])], dim=3) * covered).contiguous()
+    col = antialias(col, rast, pos, faces)[0]
+    mask = col[..., 3:4]
+    bg = 1.0 if whitebackground else 0.0
+    image = torch.where(mask != 0, col[..., :3], torch.full_like(col[..., :3], bg)).clamp(0.0, 1.0)
+    return image.permute(2, 0, 1)
 
 
 def render_mask(glctx, verts, faces, cam, resolution=None):

@@ -24,16 +24,21 @@ def _chunk(tag, data):
     return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
 
 
-def write_png(path, image, compress_level=6):
-    """image: (H, W, 3) uint8 (a numpy array, or anything np.asarray takes)."""
+def encode_png(image, compress_level=6):
+    """The bytes of write_png's file.  image: (H, W, 3) uint8 (a numpy array, or anything np.asarray takes)."""
     a = np.asarray(image)
     if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
         raise ValueError(f"write_png: image must be (H, W, 3) uint8, got {a.dtype} {a.shape}")
     H, W = a.shape[:2]
     rows = np.zeros((H, 1 + W * 3), np.uint8)  # (a leading 0 per row: filter type None)
     rows[:, 1:] = a.reshape(H, W * 3)
-    data = (b"\x89PNG\r\n\x1a\n" + _chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0))
+    return (b"\x89PNG\r\n\x1a\n" + _chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0))
             + _chunk(b"IDAT", zlib.compress(rows.tobytes(), compress_level)) + _chunk(b"IEND", b""))
+
+
+def write_png(path, image, compress_level=6):
+    """image: (H, W, 3) uint8 (a numpy array, or anything np.asarray takes)."""
+    data = encode_png(image, compress_level)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "wb") as fh:
         fh.write(data)
@@ -148,6 +153,38 @@ def parse_png_any(src):
     channels = _ANY_CHANNELS[colour]
     row_bytes = (W * channels * depth + 7) // 8
     return W, H, colour, depth, row_bytes, max(1, channels * depth // 8), _inflate_rows(bad, idat, H, row_bytes, "row bytes")
+
+
+def read_png_host(src):
+    """src: a path or the file's bytes -> (H, W, channels) uint8 numpy array of an 8-bit RGB / RGBA PNG, decoded on the host.  For the
+    small files this project writes itself (write_png: filter type 0 on every row, one reshape); rows with other filter types are
+    unfiltered one by one in numpy -- Sub, Average and Paeth byte by byte, so a large foreign file is slow.  The dataset path is
+    decode_pngs."""
+    W, H, ch, filtered = parse_png(src)
+    rows = np.frombuffer(filtered, np.uint8).reshape(H, 1 + W * ch)
+    types, out = rows[:, 0], rows[:, 1:].copy()
+    if not types.any():
+        return out.reshape(H, W, ch)
+    zero = np.zeros(W * ch, np.uint8)
+    for y in range(H):
+        t, up = int(types[y]), (out[y - 1] if y else zero)
+        if t == 2:
+            out[y] += up
+        elif t:
+            cur, upi = out[y].astype(np.int64), up.astype(np.int64)
+            for x in range(W * ch):
+                a = cur[x - ch] if x >= ch else 0
+                b, c = upi[x], (upi[x - ch] if x >= ch else 0)
+                if t == 1:
+                    pred = a
+                elif t == 3:
+                    pred = (a + b) // 2
+                else:
+                    pa, pb, pc = abs(b - c), abs(a - c), abs(a + b - 2 * c)
+                    pred = a if pa <= pb and pa <= pc else (b if pb <= pc else c)
+                cur[x] = (cur[x] + pred) & 255
+            out[y] = cur.astype(np.uint8)
+    return out.reshape(H, W, ch)
 
 
 def unfilter(filtered, B, W, H, channels):

@@ -574,6 +574,42 @@ int dgm_tri_antialias_forward(int V, int F, int H, int W, int C, const float* co
 int dgm_tri_antialias_backward(int V, int F, int H, int W, int C, const float* color, const float* rast, const float* pos, const int* tri,
                                const char* scratch, const float* dout, float* dcolor, float* dpos, void* stream);
 
+/* ---- texture sampling and the texture atlas (csrc/mesh_texture.hip) -------------------------------------------------------------------
+ * nvdiffrast.torch.texture without mip-maps (the reference samples with it in dgmesh/nvdiffrast_utils/regularizer.py:24), and the
+ * atlas that mesh_texture.py bakes appearance into.  Every buffer is device memory; nothing is allocated and nothing is read back.
+ * fp32, no FMA; csrc/mesh_texture.hip states every formula and the operation order.
+ *   dgm_tri_texture_forward: tex (Ht, Wt, C), uv (n, 2) -> out (n, C).  Texel (i, j) is centred at u = (i + .5) / Wt, v = (j + .5) / Ht;
+ *       row 0 of memory is at v = 0.  filter DGM_TEX_LINEAR: bilinear over the four texels around (u Wt - .5, v Ht - .5);
+ *       DGM_TEX_NEAREST: texel (floor(u Wt), floor(v Ht)).  boundary DGM_TEX_WRAP: indices modulo the size; DGM_TEX_CLAMP: indices
+ *       clamped; DGM_TEX_ZERO: texels outside count as 0.  A sample with a non-finite u or v gives 0 in every channel; a finite uv
+ *       of any magnitude is reduced in float before it is converted, so nothing is read outside tex.  1 <= Ht, Wt <= 16384.
+ *       With C == 4 and 16-byte aligned tex and out a texel is one 16-byte access; 4-byte alignment otherwise.  Bit-reproducible.
+ *   dgm_tri_texture_backward: dtex (Ht, Wt, C) (zeroed by the call, summed with fp32 atomics: agrees to rounding, not bit for bit, run
+ *       to run) and duv (n, 2) (plain stores, from the bilinear weights' derivatives; zero for DGM_TEX_NEAREST and for a non-finite
+ *       sample, which adds nothing to dtex either).
+ *   dgm_atlas_uv: the atlas gives each pair of faces (2c, 2c + 1) the square cell c of `cell` = s >= 4 texels a side, size / s cells
+ *       a row (size <= 16384), L = s - 3; in texel-centre index coordinates local to the cell face 2c has its corners at (0, 0),
+ *       (L, 0), (0, L) and face 2c + 1 at (s - 1, s - 1), (2, s - 1), (s - 1, 2).  uv_out (F, 3, 2): a corner at local (i, j) of cell
+ *       (cx, cy) has u = ((float)(cx s + i) + .5f) / (float)size, v alike.  More face pairs than cells is an error.
+ *   dgm_atlas_interpolate: one value per texel: out (size, size, C) and face_id (size, size), every texel written.  Local texel (i, j)
+ *       belongs to face 2c when i + j <= s - 2 (b1 = i / L, b2 = j / L), to face 2c + 1 when i + j >= s (b1 = (s - 1 - i) / L,
+ *       b2 = (s - 1 - j) / L), to nobody when i + j = s - 1; b0 = (1 - b1) - b2, NOT clamped: texels of a chart's bilinear footprint
+ *       outside the triangle hold the affine extrapolation.  Owned: out = (b0 a0 + b1 a1) + b2 a2 of attr (V, C) at the face's
+ *       corners, face_id = the face.  Unowned -- the diagonal, the margin right of or below the last whole cell, a face >= F, a face
+ *       with an index outside [0, V) (checked before any use) -- : zeros and -1.  Bit-reproducible. */
+#define DGM_TEX_NEAREST 0
+#define DGM_TEX_LINEAR 1
+#define DGM_TEX_WRAP 0
+#define DGM_TEX_CLAMP 1
+#define DGM_TEX_ZERO 2
+int dgm_tri_texture_forward(int n, int Ht, int Wt, int C, int filter, int boundary, const float* tex, const float* uv, float* out,
+                            void* stream);
+int dgm_tri_texture_backward(int n, int Ht, int Wt, int C, int filter, int boundary, const float* tex, const float* uv, const float* dout,
+                             float* dtex, float* duv, void* stream);
+int dgm_atlas_uv(int F, int size, int cell, float* uv_out, void* stream);
+int dgm_atlas_interpolate(int V, int F, int C, int size, int cell, const float* attr, const int* faces, float* out, int* face_id,
+                          void* stream);
+
 /* ---- Gaussian-mesh anchoring (csrc/anchor.hip) --------------------------------------------------------------------------------
  * Replace the trimesh / pytorch3d.knn_points / torch.unique work of GaussianModelDPSRDynamicAnchor.anchor_mesh
  * (dgmesh/scene/gaussian_model_dpsr_dynamic_anchor.py:745-829).  Every buffer is device memory; nothing is read back.
