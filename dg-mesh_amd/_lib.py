@@ -158,6 +158,11 @@ SYMBOLS = {
     "dgm_mesh_smooth_step": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _c.c_double, _i, _vp, _vp]),
     "dgm_wind_scratch_bytes": (_c.c_size_t, [_i, _i]),
     "dgm_wind_number": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_ray_accel_bytes": (_c.c_size_t, [_i]),
+    "dgm_ray_build_scratch_bytes": (_c.c_size_t, [_i]),
+    "dgm_ray_build": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_ray_cast": (_i, [_i, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dgm_ray_occluded": (_i, [_i, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "dgm_surf_closest_scratch_bytes": (_c.c_size_t, [_i, _i]),
     "dgm_surf_closest": (_i, [_i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
     "dgm_surf_interp": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp]),

@@ -28,7 +28,11 @@ Deliberately out of scope:
   * seams: there are none to hide, each face is its own chart (minified far below one texel per cell, neighbouring charts do mix);
   * any glTF feature beyond glb_io's docstring.  The glTF files are not checked against an external loader: none was available.
 
-Command line: python -m dgmesh_amd.mesh_texture in.ply out.obj|out.glb (--size N | --cell S) bakes a PLY's vertex colours."""
+bake_ambient_occlusion() bakes the mesh's self-shadowing into the same atlas by ray casting (mesh_ray.py, DESIGN.md section 4.19);
+TextureSpec(ao_samples=N) and --ao N multiply the colour texture by it, so that an exported mesh does not look flat in a viewer that
+does not light it.
+
+Command line: python -m dgmesh_amd.mesh_texture in.ply out.obj|out.glb (--size N | --cell S) [--ao N] bakes a PLY's vertex colours."""
 import argparse
 import ctypes
 import math
@@ -55,13 +59,16 @@ class Atlas(NamedTuple):
 
 @dataclass(frozen=True)
 class TextureSpec:
-    """The parameters of the textured export: the atlas (size, or cell when given) and the file format."""
+    """The parameters of the textured export: the atlas (size, or cell when given), the file format and ao_samples -- 0: the colour
+    texture as baked; > 0: multiplied by the ambient occlusion of that many rays per texel (bake_ambient_occlusion)."""
     size: Optional[int] = 2048
     cell: Optional[int] = None
     format: str = "obj"
+    ao_samples: int = 0
 
     def describe(self):
-        return (f"cell {int(self.cell)}" if self.cell is not None else f"size {int(self.size)}") + f" format {self.format}"
+        return ((f"cell {int(self.cell)}" if self.cell is not None else f"size {int(self.size)}") + f" format {self.format}"
+                + (f" ao {int(self.ao_samples)}" if self.ao_samples else ""))
 
     def atlas_args(self):
         return {"cell": self.cell} if self.cell is not None else {"size": self.size}
@@ -77,6 +84,8 @@ def as_spec(texture):
         raise TypeError(f"mesh_texture: texture must be None, a TextureSpec or a dict of its fields, got {type(texture).__name__}")
     if spec is not None and spec.format not in FORMATS:
         raise ValueError(f"mesh_texture: format must be one of {', '.join(FORMATS)}, got {spec.format!r}")
+    if spec is not None and int(spec.ao_samples) < 0:
+        raise ValueError(f"mesh_texture: ao_samples must be >= 0, got {spec.ao_samples}")
     return spec
 
 
@@ -177,6 +186,42 @@ def bake_vertex_colors(verts, faces, colors, *, size=None, cell=None):
     return tex, atlas_uv(atlas, tex.device), atlas
 
 
+def bake_ambient_occlusion(verts, faces, *, size=None, cell=None, samples=64, max_dist=math.inf, offset=None, seed=0, flip=False,
+                           accel="auto"):
+    """The ambient occlusion of the mesh per texel of its atlas: (tex (size, size, 1), uv (F, 3, 2), atlas).  Per owned texel the
+    position is atlas_interpolate(verts) and the normal the unit (v1 - v0) x (v2 - v0) of the owning face (negated with flip, for a
+    mesh wound inwards); the value is mesh_ray.ambient_occlusion there (samples, max_dist, offset, seed as it takes them), the texel
+    counting as point number "its rank among the owned texels".  Unowned texels and texels of a face without area hold 1, so that
+    multiplying a colour texture by this one changes nothing there.  One read-back (the number of owned texels)."""
+    from . import mesh_ray
+    atlas = build_atlas(int(faces.shape[0]), size=size, cell=cell)
+    pos, face_id = atlas_interpolate(atlas, verts, faces)
+    verts, faces = verts.detach().contiguous(), faces.contiguous()
+    owned = (face_id.reshape(-1) >= 0).nonzero().reshape(-1)
+    points = pos.reshape(-1, 3)[owned].contiguous()
+    corner = verts[faces[face_id.reshape(-1)[owned].long()].long()]  # (n, 3, 3)
+    normal = torch.linalg.cross(corner[:, 1] - corner[:, 0], corner[:, 2] - corner[:, 0])
+    if flip:
+        normal = -normal
+    held = accel if not (isinstance(accel, str) and accel == "auto") else mesh_ray._resolve("bake_ambient_occlusion", verts, faces, accel)[2]
+    ao = mesh_ray.ambient_occlusion(points, normal.contiguous(), verts, faces, samples, max_dist, offset, seed, held)
+    ao = torch.where(normal.abs().sum(dim=1) > 0, ao, torch.ones_like(ao))
+    tex = torch.ones(atlas.size * atlas.size, dtype=torch.float32, device=pos.device)
+    tex[owned] = ao
+    return tex.reshape(atlas.size, atlas.size, 1), atlas_uv(atlas, pos.device), atlas
+
+
+def apply_ambient_occlusion(tex, verts, faces, spec_or_samples, *, size=None, cell=None, **kwargs):
+    """tex (size, size, 3) times bake_ambient_occlusion of the same atlas; tex itself when the sample count is 0."""
+    samples = int(getattr(spec_or_samples, "ao_samples", spec_or_samples))
+    if samples <= 0:
+        return tex
+    ao = bake_ambient_occlusion(verts, faces, size=size, cell=cell, samples=samples, **kwargs)[0]
+    if tuple(ao.shape[:2]) != tuple(tex.shape[:2]):
+        raise ValueError(f"mesh_texture.apply_ambient_occlusion: the texture is {tuple(tex.shape)}, the atlas gives {tuple(ao.shape)}")
+    return tex * ao
+
+
 def appearance_color_fn(mesh, deform_back, fid):
     """The colour of evaluate.mesh_and_colors at arbitrary points: points -> mesh.appearance.step(points + deform_back.step(points, t)[0], t)
     with t the one-element tensor `fid` repeated per point."""
@@ -203,6 +248,7 @@ def build_parser():
     group = ap.add_mutually_exclusive_group(required=True)
     group.add_argument("--size", type=int, help="the texture's side in texels")
     group.add_argument("--cell", type=int, help="texels a side per pair of faces (>= 4)")
+    ap.add_argument("--ao", type=int, default=0, metavar="N", help="multiply the texture by the ambient occlusion of N rays per texel (0: none)")
     return ap
 
 
@@ -219,7 +265,10 @@ def main(argv=None):
     # (the byte k is stored as (k + 0.5) / 255: the writers' clamp(c * 255) truncated gives k back at the vertices)
     col = (colors[:, :3].astype(np.float32) + np.float32(0.5)) / np.float32(255.0)
     v, f = torch.from_numpy(verts).to(dev), torch.from_numpy(faces).to(dev)
+    if args.ao < 0:
+        raise SystemExit(f"mesh_texture: --ao must be >= 0, got {args.ao}")
     tex, uv, atlas = bake_vertex_colors(v, f, torch.from_numpy(col).to(dev), size=args.size, cell=args.cell)
+    tex = apply_ambient_occlusion(tex, v, f, args.ao, size=args.size, cell=args.cell)
     out = write_textured(stem, ext.lower()[1:], verts, faces, uv, tex)
     print(f"mesh_texture: V {len(verts)} F {len(faces)}  size {atlas.size} cell {atlas.cell}  -> {out}")
     return 0

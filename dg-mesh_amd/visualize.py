@@ -393,7 +393,8 @@ def export_dynamic_mesh(gaussians, deform, deform_back, mesh, out_dir, frames=20
     colours are untouched by it.  texture: None, or a mesh_texture.TextureSpec (or a dict of its fields): every frame ALSO gets
     dynamic_mesh_textured/frame_{i}.obj (+ .mtl, .png) or .glb, the written mesh with a texture atlas baked after `clean` / `smooth` /
     `simplify` from the appearance network itself (mesh_texture.bake with appearance_color_fn at the frame's time), not from the
-    decimated vertex colours; the PLY files are what they are without it.  -> the list of the PLY paths."""
+    decimated vertex colours; with ao_samples > 0 the texture is multiplied by the baked ambient occlusion
+    (mesh_texture.bake_ambient_occlusion); the PLY files are what they are without it.  -> the list of the PLY paths."""
     from . import mesh_clean, mesh_simplify, mesh_smooth, mesh_texture
     from .evaluate import mesh_and_colors
     from .ply_io import write_mesh_ply
@@ -419,5 +420,6 @@ def export_dynamic_mesh(gaussians, deform, deform_back, mesh, out_dir, frames=20
         if tex_spec is not None:
             tex, uv, _ = mesh_texture.bake(verts.contiguous(), faces.contiguous(), mesh_texture.appearance_color_fn(mesh, deform_back, fid),
                                            **tex_spec.atlas_args())
+            tex = mesh_texture.apply_ambient_occlusion(tex, verts.contiguous(), faces.contiguous(), tex_spec, **tex_spec.atlas_args())
             mesh_texture.write_textured(os.path.join(out_dir, "dynamic_mesh_textured", f"frame_{i}"), tex_spec.format, verts, faces, uv, tex)
     return paths

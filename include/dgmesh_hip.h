@@ -70,7 +70,8 @@ extern "C" {
  *      (rendering a checkpoint), dgm_emd_* (mesh evaluation), dgm_png_unfilter / dgm_image_ingest (reading a dataset),
  *      dgm_image_composite_bytes / dgm_resample (resizing a dataset's images), dgm_lpips* (LPIPS of the test views),
  *      dgm_png_expand / dgm_image_ingest_masked / dgm_resample_nearest (real captures: mask PNGs and masked frames); dgm_png_unfilter
- *      also takes channels = 1; dgm_mesh_* (cleaning an extracted mesh); dgm_surf_* / dgm_corr_palette (mesh correspondence). */
+ *      also takes channels = 1; dgm_mesh_* (cleaning an extracted mesh); dgm_surf_* / dgm_corr_palette (mesh correspondence);
+ *      dgm_ray_* (ray casting against a mesh). */
 #define DGM_ABI_VERSION 5
 
 /* Allocator callback: must return a device pointer to at least `bytes` bytes (128-byte aligned),
@@ -873,6 +874,41 @@ int dgm_mesh_smooth_step(int V, int A, const float* verts_in, const int* adj_off
  *       may be NULL) when F <= 16384.  N x slices beyond 2^31 - 1 workgroups of 256 queries is refused: split N. */
 size_t dgm_wind_scratch_bytes(int N, int F);
 int dgm_wind_number(int N, int V, int F, const float* points, const float* verts, const int* faces, char* scratch, float* w, void* stream);
+
+/* ---- ray casting against a triangle mesh: nearest hit, any hit (csrc/mesh_ray.hip) ---------------------------------------------------
+ * What answers what a ray hits first (mesh_ray.py: ray_cast, occluded, visible, depth_map, ambient_occlusion).  origins, dirs (N, 3),
+ * verts (V, 3) fp32, faces (F, 3) int32; every buffer is device memory, nothing is allocated and nothing is read back.
+ * PAIR TEST.  The watertight test of Woop, Benthin and Wald (JCGT 2013) in fp32 without contraction, / correctly rounded: with kz the
+ *       axis of largest |d| (ties: the lowest index), kx = kz + 1, ky = kx + 1 (mod 3), swapped when d[kz] < 0, Sx = d[kx] / d[kz],
+ *       Sy = d[ky] / d[kz], Sz = 1 / d[kz], and per corner a = v - o, Ax = a[kx] - Sx a[kz], Ay = a[ky] - Sy a[kz], Az = Sz a[kz]:
+ *       U = Cx By - Cy Bx, V = Ax Cy - Ay Cx, W = Bx Ay - By Ax; when one of them is exactly 0 all three are taken again in fp64 from
+ *       the fp32 sheared coordinates (exact products, exact signs; the sign test reads the fp64 values, then they are rounded to
+ *       fp32); a miss when one is < 0 and one > 0; det = (U + V) + W, a miss when det == 0; t = ((U Az + V Bz) + W Cz) / det,
+ *       accepted when t_min <= t < t_max and t is finite; bary = (U, V, W) / det.  The order of every operation is written out at the
+ *       head of csrc/mesh_ray.hip.  Seen from the two faces of a shared edge the edge's value is one number and its exact negation,
+ *       and a zero counts for both: no ray slips between faces that share an edge or a vertex.  d is not normalised: t is in units
+ *       of |d|.
+ * ANSWER.  The lexicographic minimum of (t, face index) over the accepted faces: independent of the visiting order, of the batch and
+ *       of the run.  None: face = -1, t = +inf, bary = 0.  Never accepted: a face with an index outside [0, V) (checked before any
+ *       use) or a non-finite corner coordinate.  A ray with a non-finite component or d = 0 gets the miss answer.  F = 0 or V = 0:
+ *       misses everywhere.  N = 0: nothing is done.  t_max <= t_min or a NaN bound: misses everywhere.
+ * TWO PATHS.  accel = NULL: a tiled brute force, N x F pairs.  accel = the structure dgm_ray_build made of the same verts and faces: the
+ *       faces sorted by the Morton code of their centroid, one box per chunk of 256; a workgroup of 256 rays tests only the chunks
+ *       whose box one of its rays may hit.  The box test rejects only what the pair test cannot accept (the argument is at the head
+ *       of csrc/mesh_ray.hip), and the candidates carry their original index: face, t and bary are the brute force's bit for bit.
+ *   dgm_ray_accel_bytes: ceil(F / 256) * (256 * 48 + 32), a function of F alone (0 for a negative or unsupported size).
+ *   dgm_ray_build_scratch_bytes: the build's scratch (0 for a negative or unsupported size); contents irrelevant, any alignment.
+ *   dgm_ray_build: writes every byte of accel (16-byte aligned).  F = 0 does nothing.  Deterministic.
+ *   dgm_ray_cast: face (N) int32, t (N) fp32, bary (N, 3) fp32.  accel NULL or 16-byte aligned.  ceil(N / 256) workgroups, which an
+ *       int N keeps inside the grid limit.  F up to 2^31 - 257.
+ *   dgm_ray_occluded: hit (N) bytes, 1 where at least one face is accepted (= face >= 0 of dgm_ray_cast), else 0. */
+size_t dgm_ray_accel_bytes(int F);
+size_t dgm_ray_build_scratch_bytes(int F);
+int dgm_ray_build(int V, int F, const float* verts, const int* faces, char* scratch, char* accel, void* stream);
+int dgm_ray_cast(int N, int V, int F, const float* origins, const float* dirs, float t_min, float t_max, const float* verts, const int* faces,
+                 const char* accel, int* face, float* t, float* bary, void* stream);
+int dgm_ray_occluded(int N, int V, int F, const float* origins, const float* dirs, float t_min, float t_max, const float* verts,
+                     const int* faces, const char* accel, unsigned char* hit, void* stream);
 
 /* ---- closest point on a triangle mesh, interpolation, correspondence colours (csrc/surface.hip) -------------------------------------
  * What carries a surface point from one frame's mesh onto another's (correspondence.py).  verts (V, 3) fp32, faces (F, 3) int32;
