@@ -230,6 +230,17 @@ def stream_ptr():
     return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(torch._C._cuda_getDevice()))
 
 
+def vp(t):
+    """The tensor's device pointer as the C ABI takes it; None or an empty tensor -> NULL."""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else None
+
+
+def scratch(nbytes, dev):
+    """Caller-owned scratch for an entry point whose *_scratch_bytes gave `nbytes` (never an empty tensor: its pointer may be NULL)."""
+    import torch
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+
+
 class _NoGuard:
     def __enter__(self):
         return None

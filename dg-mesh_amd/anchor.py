@@ -24,7 +24,6 @@ Kept as the reference does it: the 0-1 mask is rebuilt from the n-1 faces of the
 out of the batch are 0-1 candidates too (randperm over n_0_1 + n_n_1 - batch).
 No CPU fallback: every function raises on CPU tensors.
 """
-import ctypes
 import math
 
 import numpy as np
@@ -37,10 +36,6 @@ from . import densify as _D
 
 GROUPS = _D.GROUPS
 ATTR = _D.ATTR
-
-
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else None
 
 
 def _need_cuda(name, *ts):
@@ -59,7 +54,7 @@ def face_geometry(verts, faces):
     cent = torch.empty((F, 3), dtype=torch.float32, device=v.device)
     nrm = torch.empty((F, 3), dtype=torch.float32, device=v.device)
     with _lib.device_guard(v.device):
-        _lib.check(_lib.lib().dgm_anchor_face_geometry(V, F, _vp(v), _vp(f), _vp(cent), _vp(nrm), _lib.stream_ptr()))
+        _lib.check(_lib.lib().dgm_anchor_face_geometry(V, F, _lib.vp(v), _lib.vp(f), _lib.vp(cent), _lib.vp(nrm), _lib.stream_ptr()))
     return cent, nrm
 
 
@@ -75,7 +70,7 @@ def _nearest_raw(queries, targets, max_d2):
     if not math.isinf(max_d2):
         scratch = torch.empty(int(L.dgm_anchor_nn_scratch_bytes(Nq, Nt)), dtype=torch.uint8, device=q.device)
     with _lib.device_guard(q.device):
-        _lib.check(L.dgm_anchor_nn(Nq, Nt, _vp(q), _vp(t), float(max_d2), _vp(scratch), _vp(idx), _vp(d2), _lib.stream_ptr()))
+        _lib.check(L.dgm_anchor_nn(Nq, Nt, _lib.vp(q), _lib.vp(t), float(max_d2), _lib.vp(scratch), _lib.vp(idx), _lib.vp(d2), _lib.stream_ptr()))
     return idx, d2
 
 
@@ -99,8 +94,8 @@ def classify(face_of, F):
     totals = torch.empty(4, dtype=torch.int32, device=dev)
     scratch = torch.empty(int(L.dgm_anchor_classify_scratch_bytes(P, F)), dtype=torch.uint8, device=dev)
     with _lib.device_guard(dev):
-        _lib.check(L.dgm_anchor_classify(P, F, _vp(fo), _vp(scratch), _vp(out["counts"]), _vp(out["offsets"]), _vp(out["lists"]),
-                                         _vp(out["members"]), _vp(out["rank"]), _vp(totals), _lib.stream_ptr()))
+        _lib.check(L.dgm_anchor_classify(P, F, _lib.vp(fo), _lib.vp(scratch), _lib.vp(out["counts"]), _lib.vp(out["offsets"]), _lib.vp(out["lists"]),
+                                         _lib.vp(out["members"]), _lib.vp(out["rank"]), _lib.vp(totals), _lib.stream_ptr()))
     out["totals"] = tuple(int(v) for v in totals.tolist())
     return out
 

@@ -20,7 +20,6 @@ summed in fp64 on the device and the table is read back once, after the last fra
 
 float32 CUDA/HIP tensors only -- no CPU fallback; anything else raises.
 """
-import ctypes
 import json
 import math
 import os
@@ -35,10 +34,6 @@ MODES = ("reference", "canonical")
 PALETTES = {"rgb": 0, "checker": 1}
 LOST_COLOR = (1.0, 0.0, 1.0)
 COLUMNS = ("n_queries", "n_found", "mean_dist", "max_dist", "mean_dist_voxels", "max_dist_voxels")
-
-
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else None
 
 
 def _need(name, t, what, dtype, shape_tail=None):
@@ -86,7 +81,7 @@ def closest_on_mesh(points, verts, faces, max_dist=math.inf):
     if not math.isinf(max_d2):
         scratch = torch.empty(int(L.dgm_surf_closest_scratch_bytes(N, F)), dtype=torch.uint8, device=dev)
     with _lib.device_guard(dev):
-        _lib.check(L.dgm_surf_closest(N, V, F, _vp(p), _vp(v), _vp(f), max_d2, _vp(scratch), _vp(face), _vp(d2), _vp(bary),
+        _lib.check(L.dgm_surf_closest(N, V, F, _lib.vp(p), _lib.vp(v), _lib.vp(f), max_d2, _lib.vp(scratch), _lib.vp(face), _lib.vp(d2), _lib.vp(bary),
                                       _lib.stream_ptr()))
     return face, d2, bary
 
@@ -110,8 +105,8 @@ def interpolate(attr, faces, face, bary, fill=math.nan):
         raise ValueError(f"correspondence.{name}: attr needs at least one channel")
     out = torch.empty((N, C) if a.dim() == 2 else (N,), dtype=torch.float32, device=a.device)
     with _lib.device_guard(a.device):
-        _lib.check(_lib.lib().dgm_surf_interp(N, V, F, C, _vp(a), _vp(faces.contiguous()), _vp(face.contiguous()),
-                                              _vp(bary.detach().contiguous()), float(fill), _vp(out), _lib.stream_ptr()))
+        _lib.check(_lib.lib().dgm_surf_interp(N, V, F, C, _lib.vp(a), _lib.vp(faces.contiguous()), _lib.vp(face.contiguous()),
+                                              _lib.vp(bary.detach().contiguous()), float(fill), _lib.vp(out), _lib.stream_ptr()))
     return out
 
 
@@ -140,7 +135,7 @@ def palette(xyz, center, scale, mode="rgb", cells=8):
     x = xyz.detach().contiguous()
     out = torch.empty_like(x)
     with _lib.device_guard(dev):
-        _lib.check(_lib.lib().dgm_corr_palette(x.shape[0], _vp(x), _vp(c), _vp(s), m, cells, _vp(out), _lib.stream_ptr()))
+        _lib.check(_lib.lib().dgm_corr_palette(x.shape[0], _lib.vp(x), _lib.vp(c), _lib.vp(s), m, cells, _lib.vp(out), _lib.stream_ptr()))
     return out
 
 

@@ -11,52 +11,25 @@
 //   * finite max_d2: a hashed uniform grid over the targets with cell edge c = 1.001 sqrt(max_d2) (at least 2^-20 of the targets'
 //     bounding-box extent, so that cell coordinates stay below 2^20).  Cell coordinates are taken in fp64 from the fp32 points, so a
 //     target with fp32 d2 < max_d2 lies within one cell of the query's cell on every axis: the 27 cells around the query hold it.
-//     Cells hash into a table of 2^k >= Nt buckets; a collision only adds candidates.  The table is built by histogram, scan and
-//     scatter; the queries are visited in the order of their own bucket so that the lanes of a wave mostly scan the same cells.
+//     Cells hash into a table of 2^k >= Nt buckets; a collision only adds candidates.  The table is built by histogram, scan
+//     (mesh_scan.hpp) and scatter, its cells are those of mesh_grid.hpp; the queries are visited in the order of their own bucket so that the lanes of a wave mostly scan the same cells.
 //   * max_d2 = +inf: a tiled brute force (256 targets per LDS tile, one query per lane) -- the unbounded knn_points(K=1).
 // Scratch is caller-owned; nothing here allocates device memory or reads anything back to the host.
 #include <float.h>
 #include <math.h>
 
-#include "dgm_common.hpp"
+#include "dgm_host.hpp"
+#include "mesh_grid.hpp"
+#include "mesh_scan.hpp"
 
 #pragma clang fp contract(off)
-
-namespace dgm {
-void launch_scan_blocks(hipStream_t st, int n, const unsigned* in, unsigned* out, unsigned* total);
-size_t radix_sort_hist_words(int n);
-const unsigned* radix_sort_pairs(hipStream_t st, int n, int passes, unsigned* keysA, unsigned* valsA, unsigned* keysB,
-                                 unsigned* valsB, unsigned* hist, unsigned* scanned);
-void set_last_error(const char* msg);
-}  // namespace dgm
 
 namespace {
 using namespace dgm;
 
 constexpr int AN_THREADS = 256;
-constexpr int SCAN_ITEMS = 16;                           // consecutive elements per thread in the block scans
-constexpr int SCAN_TILE = AN_THREADS * SCAN_ITEMS;       // elements per scan workgroup
-constexpr int BF_TILE = 256;                             // targets per LDS tile of the brute force
+constexpr int BF_TILE = 256;  // targets per LDS tile of the brute force
 constexpr int BBOX_PARTS = 128;
-constexpr double CELL_LIMIT = 1048576.0;                 // cells per axis at most (2^20)
-constexpr int CELL_CLAMP = (1 << 20) + 3;
-
-unsigned blocks(long long n, int t = AN_THREADS) { return (unsigned)((n + t - 1) / t); }
-
-int afail(const char* m) {
-    set_last_error(m);
-    return 1;
-}
-int adone() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : afail(hipGetErrorString(e));
-}
-
-size_t pow2_at_least(size_t n) {
-    size_t h = 64;
-    while (h < n) h <<= 1;
-    return h;
-}
 
 // ---- face geometry -------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(AN_THREADS)
@@ -92,155 +65,19 @@ face_geometry_kernel(int V, int F, const float* __restrict__ verts, const int* _
     nrm[3 * f + 2] = ok ? nz / len : 0.f;
 }
 
-// ---- three-phase exclusive scans of up to three u32 components (tiles of SCAN_TILE elements) --------------------------------------
-struct U3 {
-    unsigned x, y, z;
-};
-
-__device__ __forceinline__ U3 block_exclusive_u3(U3 v, U3* wave_tot, U3& total) {
-    const int lane = lane_id(), wv = threadIdx.x >> 6;
-    const unsigned ix = wave_inclusive_scan_u32(v.x), iy = wave_inclusive_scan_u32(v.y), iz = wave_inclusive_scan_u32(v.z);
-    if (lane == 63) wave_tot[wv] = U3{ix, iy, iz};
-    __syncthreads();
-    U3 pre{0u, 0u, 0u};
-    total = U3{0u, 0u, 0u};
-    for (int w = 0; w < AN_THREADS / 64; w++) {
-        const U3 t = wave_tot[w];
-        if (w < wv) {
-            pre.x += t.x;
-            pre.y += t.y;
-            pre.z += t.z;
-        }
-        total.x += t.x;
-        total.y += t.y;
-        total.z += t.z;
-    }
-    __syncthreads();
-    return U3{pre.x + ix - v.x, pre.y + iy - v.y, pre.z + iz - v.z};
-}
-
-// phase A: per-tile totals, one array per component (SoA: each is scanned by launch_scan_blocks)
-template <class Val>
-__global__ void __launch_bounds__(AN_THREADS) scan_tiles_kernel(long long n, Val val, unsigned* __restrict__ tx, unsigned* __restrict__ ty,
-                                                                unsigned* __restrict__ tz) {
-    __shared__ U3 wave_tot[AN_THREADS / 64];
-    const long long base = (long long)blockIdx.x * SCAN_TILE + (long long)threadIdx.x * SCAN_ITEMS;
-    U3 s{0u, 0u, 0u};
-    for (int k = 0; k < SCAN_ITEMS; k++) {
-        if (base + k < n) {
-            const U3 v = val(base + k);
-            s.x += v.x;
-            s.y += v.y;
-            s.z += v.z;
-        }
-    }
-    U3 total;
-    block_exclusive_u3(s, wave_tot, total);
-    if (threadIdx.x == 0) {
-        tx[blockIdx.x] = total.x;
-        if (ty) ty[blockIdx.x] = total.y;
-        if (tz) tz[blockIdx.x] = total.z;
-    }
-}
-
-// phase C: emit(i, value, exclusive prefix) for every element, in index order within a thread
-template <class Val, class Emit>
-__global__ void __launch_bounds__(AN_THREADS) scan_emit_kernel(long long n, Val val, Emit emit, const unsigned* __restrict__ ox,
-                                                               const unsigned* __restrict__ oy, const unsigned* __restrict__ oz) {
-    __shared__ U3 wave_tot[AN_THREADS / 64];
-    const long long base = (long long)blockIdx.x * SCAN_TILE + (long long)threadIdx.x * SCAN_ITEMS;
-    U3 s{0u, 0u, 0u};
-    for (int k = 0; k < SCAN_ITEMS; k++) {
-        if (base + k < n) {
-            const U3 v = val(base + k);
-            s.x += v.x;
-            s.y += v.y;
-            s.z += v.z;
-        }
-    }
-    U3 total;
-    U3 pre = block_exclusive_u3(s, wave_tot, total);
-    pre.x += ox[blockIdx.x];
-    if (oy) pre.y += oy[blockIdx.x];
-    if (oz) pre.z += oz[blockIdx.x];
-    for (int k = 0; k < SCAN_ITEMS; k++) {
-        if (base + k < n) {
-            const U3 v = val(base + k);
-            emit(base + k, v, pre);
-            pre.x += v.x;
-            pre.y += v.y;
-            pre.z += v.z;
-        }
-    }
-}
-
-int scan_blocks(long long n) { return (int)((n + SCAN_TILE - 1) / SCAN_TILE); }
-
 // ---- grid helpers --------------------------------------------------------------------------------------------------------------
-struct GridParams {
-    double origin[3];
-    double inv;  // 1 / cell edge
-};
-
-__global__ void __launch_bounds__(256)
-bbox_partial_kernel(int n, const float* __restrict__ pts, float* __restrict__ partial) {
-    __shared__ float red[6][256];
-    float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+__global__ void __launch_bounds__(BOX_THREADS) bbox_partial_kernel(int n, const float* __restrict__ pts, float* __restrict__ partial) {
+    float v[6];
+    box_start<6>(v);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {  // ends at n
 #pragma unroll
         for (int a = 0; a < 3; a++) {
-            const float v = pts[3 * i + a];  // (fminf / fmaxf drop NaN)
-            mn[a] = fminf(mn[a], v);
-            mx[a] = fmaxf(mx[a], v);
+            const float x = pts[3 * i + a];
+            v[a] = box_join(a, v[a], x);
+            v[3 + a] = box_join(3 + a, v[3 + a], x);
         }
     }
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        red[a][threadIdx.x] = mn[a];
-        red[3 + a][threadIdx.x] = mx[a];
-    }
-    __syncthreads();
-    for (int off = 128; off >= 1; off >>= 1) {
-        if ((int)threadIdx.x < off) {
-#pragma unroll
-            for (int a = 0; a < 3; a++) {
-                red[a][threadIdx.x] = fminf(red[a][threadIdx.x], red[a][threadIdx.x + off]);
-                red[3 + a][threadIdx.x] = fmaxf(red[3 + a][threadIdx.x], red[3 + a][threadIdx.x + off]);
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x < 6) partial[blockIdx.x * 6 + threadIdx.x] = red[threadIdx.x][0];
-}
-
-__global__ void grid_params_kernel(int nparts, const float* __restrict__ partial, float max_d2, GridParams* __restrict__ gp) {
-    if (threadIdx.x != 0) return;
-    float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-    for (int b = 0; b < nparts; b++)
-        for (int a = 0; a < 3; a++) {
-            lo[a] = fminf(lo[a], partial[b * 6 + a]);
-            hi[a] = fmaxf(hi[a], partial[b * 6 + 3 + a]);
-        }
-    double ext = 0.0;
-    for (int a = 0; a < 3; a++) {
-        const bool finite = lo[a] <= hi[a];  // (no finite target at all: any origin will do)
-        gp->origin[a] = finite ? (double)lo[a] : 0.0;
-        if (finite) ext = fmax(ext, (double)hi[a] - (double)lo[a]);
-    }
-    double cell = 1.001 * sqrt((double)max_d2);
-    cell = fmax(cell, ext / CELL_LIMIT);
-    gp->inv = cell > 0.0 ? 1.0 / cell : 1.0;
-}
-
-__device__ __forceinline__ int cell_coord(float p, double o, double inv) {
-    double u = floor(((double)p - o) * inv);
-    if (!(u >= -2.0)) u = -2.0;  // (NaN included)
-    if (u > (double)CELL_CLAMP) u = (double)CELL_CLAMP;
-    return (int)u;
-}
-
-__device__ __forceinline__ unsigned cell_hash(int ix, int iy, int iz, unsigned mask) {
-    return (((unsigned)ix * 73856093u) ^ ((unsigned)iy * 19349663u) ^ ((unsigned)iz * 83492791u)) & mask;
+    box_reduce_partial<6>(v, partial);
 }
 
 // bucket of every point (targets: into `mask + 1` buckets; queries: the same hash into their own table), counted
@@ -255,19 +92,6 @@ bucket_count_kernel(int n, const float* __restrict__ pts, const GridParams* __re
     key[i] = b;
     atomicAdd(&cnt[b], 1u);
 }
-
-struct LoadU32 {
-    const unsigned* v;
-    __device__ U3 operator()(long long i) const { return U3{v[i], 0u, 0u}; }
-};
-struct StoreExcl {
-    unsigned* out;
-    unsigned* cursor;
-    __device__ void operator()(long long i, U3, U3 pre) const {
-        out[i] = pre.x;
-        cursor[i] = pre.x;
-    }
-};
 
 __global__ void __launch_bounds__(AN_THREADS)
 target_scatter_kernel(int n, const float* __restrict__ pts, const unsigned* __restrict__ key, unsigned* __restrict__ cursor,
@@ -357,7 +181,7 @@ NnLayout nn_layout(int Nq, int Nt) {
     NnLayout L;
     L.Ht = pow2_at_least((size_t)Nt);
     L.Hq = pow2_at_least((size_t)Nq);
-    const size_t nb = (size_t)scan_blocks((long long)(L.Ht > L.Hq ? L.Ht : L.Hq));
+    const size_t nb = (size_t)scan_tiles((long long)(L.Ht > L.Hq ? L.Ht : L.Hq));
     size_t o = 0;
     auto take = [&](size_t bytes) {
         const size_t at = o;
@@ -382,12 +206,7 @@ NnLayout nn_layout(int Nq, int Nt) {
 
 // exclusive scan of cnt[0, H) into start[0, H] (start[H] = the total) and cursor[0, H)
 void scan_counts(hipStream_t st, size_t H, const unsigned* cnt, unsigned* start, unsigned* cursor, unsigned* tiles) {
-    const int nb = scan_blocks((long long)H);
-    hipLaunchKernelGGL(scan_tiles_kernel<LoadU32>, dim3(nb), dim3(AN_THREADS), 0, st, (long long)H, LoadU32{cnt}, tiles,
-                       (unsigned*)nullptr, (unsigned*)nullptr);
-    launch_scan_blocks(st, nb, tiles, tiles + nb, start + H);
-    hipLaunchKernelGGL((scan_emit_kernel<LoadU32, StoreExcl>), dim3(nb), dim3(AN_THREADS), 0, st, (long long)H, LoadU32{cnt},
-                       StoreExcl{start, cursor}, (const unsigned*)(tiles + nb), (const unsigned*)nullptr, (const unsigned*)nullptr);
+    scan_exclusive(st, (long long)H, cnt, tiles, tiles + scan_tiles((long long)H), start, cursor, true, start + H);
 }
 
 // ---- classification ------------------------------------------------------------------------------------------------------------
@@ -405,25 +224,27 @@ face_count_kernel(int P, int F, const int* __restrict__ face_of, unsigned* __res
 
 struct FaceClass {  // (count, is 1-1, is n-1) of a face
     const unsigned* counts;
-    __device__ U3 operator()(long long f) const {
+    __device__ void operator()(long long f, unsigned* x) const {
         const unsigned c = counts[f];
-        return U3{c, c == 1u ? 1u : 0u, c > 1u ? 1u : 0u};
+        x[0] = c;
+        x[1] = c == 1u ? 1u : 0u;
+        x[2] = c > 1u ? 1u : 0u;
     }
 };
 struct FaceEmit {
     int* offsets;
     int* lists;
     const unsigned* totals;  // (n11, nn1) after the tile scan
-    __device__ void operator()(long long f, U3 v, U3 pre) const {
-        offsets[f] = (int)pre.x;
+    __device__ void operator()(long long f, const unsigned* v, const unsigned* pre) const {
+        offsets[f] = (int)pre[0];
         const unsigned n11 = totals[1], nn1 = totals[2];
         long long at;
-        if (v.y)
-            at = pre.y;
-        else if (v.z)
-            at = (long long)n11 + pre.z;
+        if (v[1])
+            at = pre[1];
+        else if (v[2])
+            at = (long long)n11 + pre[2];
         else
-            at = (long long)n11 + nn1 + (f - pre.y - pre.z);
+            at = (long long)n11 + nn1 + (f - pre[1] - pre[2]);
         lists[at] = (int)f;
     }
 };
@@ -455,7 +276,7 @@ struct ClassifyLayout {
 
 ClassifyLayout classify_layout(int P, int F) {
     ClassifyLayout L;
-    L.nb = scan_blocks(F);
+    L.nb = scan_tiles(F);
     const size_t n = (size_t)P, hw = radix_sort_hist_words(P);
     size_t o = 0;
     auto take = [&](size_t bytes) {
@@ -480,12 +301,12 @@ ClassifyLayout classify_layout(int P, int F) {
 extern "C" {
 
 int dgm_anchor_face_geometry(int V, int F, const float* verts, const int* faces, float* centroids, float* normals, void* stream) {
-    if (V < 0 || F < 0) return afail("anchor_face_geometry: need V >= 0 and F >= 0");
-    if (F == 0) return adone();
-    if (!faces || !centroids || !normals || (V > 0 && !verts)) return afail("anchor_face_geometry: NULL pointer");
+    if (V < 0 || F < 0) return fail("anchor_face_geometry: need V >= 0 and F >= 0");
+    if (F == 0) return launch_status();
+    if (!faces || !centroids || !normals || (V > 0 && !verts)) return fail("anchor_face_geometry: NULL pointer");
     hipLaunchKernelGGL(face_geometry_kernel, dim3(blocks(F)), dim3(AN_THREADS), 0, (hipStream_t)stream, V, F, verts, faces, centroids,
                        normals);
-    return adone();
+    return launch_status();
 }
 
 size_t dgm_anchor_nn_scratch_bytes(int Nq, int Nt) {
@@ -495,19 +316,19 @@ size_t dgm_anchor_nn_scratch_bytes(int Nq, int Nt) {
 
 int dgm_anchor_nn(int Nq, int Nt, const float* queries, const float* targets, float max_d2, char* scratch, int* idx, float* d2,
                   void* stream) {
-    if (Nq < 0 || Nt < 0) return afail("anchor_nn: need Nq >= 0 and Nt >= 0");
-    if (Nq == 0) return adone();
-    if (!queries || !idx || !d2 || (Nt > 0 && !targets)) return afail("anchor_nn: NULL pointer");
+    if (Nq < 0 || Nt < 0) return fail("anchor_nn: need Nq >= 0 and Nt >= 0");
+    if (Nq == 0) return launch_status();
+    if (!queries || !idx || !d2 || (Nt > 0 && !targets)) return fail("anchor_nn: NULL pointer");
     hipStream_t st = (hipStream_t)stream;
     if (Nt == 0 || !(max_d2 > 0.f)) {  // nothing can be reported (NaN bound included)
         hipLaunchKernelGGL(nn_none_kernel, dim3(blocks(Nq)), dim3(AN_THREADS), 0, st, Nq, idx, d2);
-        return adone();
+        return launch_status();
     }
     if (isinf(max_d2)) {
         hipLaunchKernelGGL(brute_query_kernel, dim3(blocks(Nq)), dim3(AN_THREADS), 0, st, Nq, Nt, queries, targets, max_d2, idx, d2);
-        return adone();
+        return launch_status();
     }
-    if (!scratch) return afail("anchor_nn: NULL scratch");
+    if (!scratch) return fail("anchor_nn: NULL scratch");
     const NnLayout L = nn_layout(Nq, Nt);
     char* base = align_ptr(scratch);
     float* partial = (float*)(base + L.partial);
@@ -518,10 +339,10 @@ int dgm_anchor_nn(int Nq, int Nt, const float* queries, const float* targets, fl
     float4* sorted = (float4*)(base + L.sorted);
     const unsigned mask_t = (unsigned)(L.Ht - 1), mask_q = (unsigned)(L.Hq - 1);
     if (hipMemsetAsync(cnt_t, 0, L.Ht * 4, st) != hipSuccess || hipMemsetAsync(cnt_q, 0, L.Hq * 4, st) != hipSuccess)
-        return afail("anchor_nn: memset failed");
+        return fail("anchor_nn: memset failed");
     const int nparts = Nt < BBOX_PARTS * 256 ? (Nt + 255) / 256 : BBOX_PARTS;
     hipLaunchKernelGGL(bbox_partial_kernel, dim3(nparts), dim3(256), 0, st, Nt, targets, partial);
-    hipLaunchKernelGGL(grid_params_kernel, dim3(1), dim3(64), 0, st, nparts, (const float*)partial, max_d2, gp);
+    hipLaunchKernelGGL(grid_params_kernel<6>, dim3(1), dim3(64), 0, st, nparts, (const float*)partial, max_d2, gp);
     hipLaunchKernelGGL(bucket_count_kernel, dim3(blocks(Nt)), dim3(AN_THREADS), 0, st, Nt, targets, (const GridParams*)gp, mask_t, key_t,
                        cnt_t);
     hipLaunchKernelGGL(bucket_count_kernel, dim3(blocks(Nq)), dim3(AN_THREADS), 0, st, Nq, queries, (const GridParams*)gp, mask_q, key_q,
@@ -533,7 +354,7 @@ int dgm_anchor_nn(int Nq, int Nt, const float* queries, const float* targets, fl
     hipLaunchKernelGGL(query_scatter_kernel, dim3(blocks(Nq)), dim3(AN_THREADS), 0, st, Nq, (const unsigned*)key_q, cursor_t, order);
     hipLaunchKernelGGL(grid_query_kernel, dim3(blocks(Nq)), dim3(AN_THREADS), 0, st, Nq, queries, (const unsigned*)order,
                        (const GridParams*)gp, mask_t, (const unsigned*)start_t, (const float4*)sorted, max_d2, idx, d2);
-    return adone();
+    return launch_status();
 }
 
 size_t dgm_anchor_classify_scratch_bytes(int P, int F) {
@@ -543,9 +364,9 @@ size_t dgm_anchor_classify_scratch_bytes(int P, int F) {
 
 int dgm_anchor_classify(int P, int F, const int* face_of, char* scratch, int* counts, int* offsets, int* lists, int* members, int* rank,
                         int* totals, void* stream) {
-    if (P < 0 || F < 0) return afail("anchor_classify: need P >= 0 and F >= 0");
+    if (P < 0 || F < 0) return fail("anchor_classify: need P >= 0 and F >= 0");
     if (!scratch || !totals || (P > 0 && (!face_of || !members || !rank)) || (F > 0 && (!counts || !offsets || !lists)))
-        return afail("anchor_classify: NULL pointer");
+        return fail("anchor_classify: NULL pointer");
     hipStream_t st = (hipStream_t)stream;
     const ClassifyLayout L = classify_layout(P, F);
     char* base = align_ptr(scratch);
@@ -553,21 +374,12 @@ int dgm_anchor_classify(int P, int F, const int* face_of, char* scratch, int* co
     unsigned *keysB = (unsigned*)(base + L.keysB), *valsB = (unsigned*)(base + L.valsB);
     unsigned *tiles = (unsigned*)(base + L.tiles), *tot = (unsigned*)(base + L.tot);
     if (hipMemsetAsync(tot, 0, 16, st) != hipSuccess || (F > 0 && hipMemsetAsync(counts, 0, (size_t)F * 4, st) != hipSuccess))
-        return afail("anchor_classify: memset failed");
+        return fail("anchor_classify: memset failed");
     if (P > 0)
         hipLaunchKernelGGL(face_count_kernel, dim3(blocks(P)), dim3(AN_THREADS), 0, st, P, F, face_of, (unsigned*)counts, keysA, valsA);
     if (F > 0) {
-        const int nb = L.nb;
-        unsigned *tx = tiles, *ty = tiles + nb, *tz = tiles + 2 * nb;
-        hipLaunchKernelGGL(scan_tiles_kernel<FaceClass>, dim3(nb), dim3(AN_THREADS), 0, st, (long long)F, FaceClass{(const unsigned*)counts},
-                           tx, ty, tz);
-        unsigned* o = tiles + 3 * nb;
-        launch_scan_blocks(st, nb, tx, o, tot);
-        launch_scan_blocks(st, nb, ty, o + nb, tot + 1);
-        launch_scan_blocks(st, nb, tz, o + 2 * nb, tot + 2);
-        hipLaunchKernelGGL((scan_emit_kernel<FaceClass, FaceEmit>), dim3(nb), dim3(AN_THREADS), 0, st, (long long)F,
-                           FaceClass{(const unsigned*)counts}, FaceEmit{offsets, lists, (const unsigned*)tot}, (const unsigned*)o,
-                           (const unsigned*)(o + nb), (const unsigned*)(o + 2 * nb));
+        scan_exclusive<3>(st, (long long)F, FaceClass{(const unsigned*)counts}, FaceEmit{offsets, lists, (const unsigned*)tot}, tiles,
+                          tiles + 3 * L.nb, tot);
     }
     hipLaunchKernelGGL(totals_kernel, dim3(1), dim3(64), 0, st, F, (const unsigned*)tot, totals);
     if (P > 0) {
@@ -579,7 +391,7 @@ int dgm_anchor_classify(int P, int F, const int* face_of, char* scratch, int* co
         const unsigned* keys = vals == valsA ? keysA : keysB;
         hipLaunchKernelGGL(rank_kernel, dim3(blocks(P)), dim3(AN_THREADS), 0, st, P, F, keys, vals, (const int*)offsets, members, rank);
     }
-    return adone();
+    return launch_status();
 }
 
 }  // extern "C"

@@ -26,7 +26,6 @@ void launch_preprocess_fwd(hipStream_t st, int P, int D, int M, const float* mea
 void launch_mark_visible(hipStream_t st, int P, const float* means3D, const float* viewmatrix, uint8_t* present);
 // binning.hip
 int binning_lds_limit_tiles();
-void launch_scan_blocks(hipStream_t st, int n, const unsigned* in, unsigned* out, unsigned* total);
 hipError_t launch_count(hipStream_t st, int P, int chunk, int nchunks, int tiles, int gridx,
                         const unsigned* tiles_touched, float* rec, const unsigned* block_sums, unsigned* offs,
                         unsigned* hist, unsigned* counters);

@@ -17,10 +17,9 @@
 // max_radii2D, :458-460).  Adam moments travel with kept originals and are zero for every new row (:429-432).
 // Split children: xyz = R(q / |q|) (exp(scaling) * z) + xyz with z ~ N(0, 1) SUPPLIED by the caller (shape [2][P][3]) --
 // a shared-seed generator makes data-parallel replicas draw identical samples.
-#include "dgm_common.hpp"
+#include "dgm_host.hpp"
 
 namespace dgm {
-void set_last_error(const char* msg);  // c_api.hip
 
 // flags: bit 0 original kept, bit 1 clone kept, bit 2 split children kept
 __global__ void __launch_bounds__(256)
@@ -177,23 +176,16 @@ densify_stats_kernel(int P, const float* __restrict__ grad2d, const int* __restr
 
 using namespace dgm;
 
-namespace {
-int dfail(const char* m) {
-    dgm::set_last_error(m);
-    return 1;
-}
-}  // namespace
-
 extern "C" {
 
 int dgm_densify_stats(int P, const float* grad2d, const int* radii, float* max_radii2D, float* grad_accum, float* denom,
                       void* stream) {
     if (P <= 0) return 0;
-    if (!radii || !max_radii2D || (grad2d && (!grad_accum || !denom))) return dfail("densify_stats: NULL pointer");
+    if (!radii || !max_radii2D || (grad2d && (!grad_accum || !denom))) return fail("densify_stats: NULL pointer");
     hipLaunchKernelGGL(densify_stats_kernel, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, grad2d, radii,
                        max_radii2D, grad_accum, denom);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return dfail(hipGetErrorString(e));
+    if (e != hipSuccess) return fail(hipGetErrorString(e));
     return 0;
 }
 
@@ -206,21 +198,21 @@ int dgm_densify_decide(int P, const float* grad_accum, const float* denom, const
                        float grad_threshold, float dense_extent, float min_opacity, float big_extent,
                        const uint8_t* keep_mask, char* scratch, void* stream) {
     if (P <= 0) return 0;
-    if (!scratch || (!keep_mask && (!grad_accum || !denom || !scaling || !opacity))) return dfail("densify_decide: NULL pointer");
+    if (!scratch || (!keep_mask && (!grad_accum || !denom || !scaling || !opacity))) return fail("densify_decide: NULL pointer");
     hipStream_t st = (hipStream_t)stream;
     const size_t Pp = (size_t)((P + 255) / 256 * 256);
     uint8_t* flags = (uint8_t*)scratch;
     unsigned* off = (unsigned*)(scratch + Pp);
     unsigned* totals = (unsigned*)(scratch + Pp * 13);
     if (keep_mask) {  // prune_points(): the caller's keep mask (bytes 0 / 1) is the flag array
-        if (hipMemcpyAsync(flags, keep_mask, (size_t)P, hipMemcpyDeviceToDevice, st) != hipSuccess) return dfail("densify_decide: copy failed");
+        if (hipMemcpyAsync(flags, keep_mask, (size_t)P, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail("densify_decide: copy failed");
     } else {
         hipLaunchKernelGGL(densify_flags_kernel, dim3((P + 255) / 256), dim3(256), 0, st, P, grad_accum, denom, scaling, opacity,
                            grad_threshold, dense_extent, min_opacity, big_extent, flags);
     }
     hipLaunchKernelGGL(densify_scan_kernel, dim3(1), dim3(1024), 0, st, P, flags, off, off + Pp, off + 2 * Pp, totals);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return dfail(hipGetErrorString(e));
+    if (e != hipSuccess) return fail(hipGetErrorString(e));
     return 0;
 }
 
@@ -233,11 +225,11 @@ int dgm_densify_apply(int P, unsigned K, unsigned C, unsigned S, const char* scr
     if (P <= 0) return 0;
     const unsigned Pn = K + C + 2u * S;
     if (Pn == 0) return 0;
-    if (!scratch || !src_scratch || !in || !out || !width || !is_moment) return dfail("densify_apply: NULL pointer");
-    if (n_tensors < 0 || n_tensors > GATHER_MAX) return dfail("densify_apply: too many tensors");
+    if (!scratch || !src_scratch || !in || !out || !width || !is_moment) return fail("densify_apply: NULL pointer");
+    if (n_tensors < 0 || n_tensors > GATHER_MAX) return fail("densify_apply: too many tensors");
     if (S > 0 && (!z || xyz_index < 0 || scaling_index < 0 || rotation_index < 0 || xyz_index >= n_tensors ||
                   scaling_index >= n_tensors || rotation_index >= n_tensors))
-        return dfail("densify_apply: split needs the samples and the xyz / scaling / rotation tensors");
+        return fail("densify_apply: split needs the samples and the xyz / scaling / rotation tensors");
     hipStream_t st = (hipStream_t)stream;
     const size_t Pp = (size_t)((P + 255) / 256 * 256);
     const uint8_t* flags = (const uint8_t*)scratch;
@@ -248,7 +240,7 @@ int dgm_densify_apply(int P, unsigned K, unsigned C, unsigned S, const char* scr
     jobs.count = n_tensors;
     int wmax = 1;
     for (int t = 0; t < n_tensors; t++) {
-        if (!in[t] || !out[t] || width[t] <= 0) return dfail("densify_apply: bad tensor entry");
+        if (!in[t] || !out[t] || width[t] <= 0) return fail("densify_apply: bad tensor entry");
         jobs.in[t] = in[t], jobs.out[t] = out[t], jobs.width[t] = width[t], jobs.is_moment[t] = is_moment[t];
         if (width[t] > wmax) wmax = width[t];
     }
@@ -261,7 +253,7 @@ int dgm_densify_apply(int P, unsigned K, unsigned C, unsigned S, const char* scr
         hipLaunchKernelGGL(densify_split_kernel, dim3((2 * S + 255) / 256), dim3(256), 0, st, P, K + C, 2 * S, src_scratch,
                            in[xyz_index], in[scaling_index], in[rotation_index], z, out[xyz_index], out[scaling_index]);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return dfail(hipGetErrorString(e));
+    if (e != hipSuccess) return fail(hipGetErrorString(e));
     return 0;
 }
 

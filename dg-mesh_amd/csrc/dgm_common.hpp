@@ -102,6 +102,15 @@ static inline char* align_ptr(char* p, size_t a = 256) {
     return (char*)(((uintptr_t)p + a - 1) / a * a);
 }
 
+// Defined in one translation unit, used by many:
+void set_last_error(const char* msg);  // c_api.hip: what dgm_last_error() returns on this thread
+// binning.hip: out[i] = the sum of in[0 .. i) for i < n in one workgroup, *total (where given) = the sum of all
+void launch_scan_blocks(hipStream_t st, int n, const unsigned* in, unsigned* out, unsigned* total);
+// knn.hip: the stable 8-bit LSD radix sort of (key, value) pairs and the u32 words its `hist` and `scanned` take each
+size_t radix_sort_hist_words(int n);
+const unsigned* radix_sort_pairs(hipStream_t st, int n, int passes, unsigned* keysA, unsigned* valsA, unsigned* keysB,
+                                 unsigned* valsB, unsigned* hist, unsigned* scanned);
+
 // ---------------------------------------------------------------------------------------------
 // device helpers
 // ---------------------------------------------------------------------------------------------
@@ -140,6 +149,15 @@ __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp
 // mode: a global_load/store_dwordx4 needs 4-byte alignment)
 typedef float dgm_f4u __attribute__((ext_vector_type(4), aligned(4)));
 typedef unsigned long long dgm_u64u __attribute__((aligned(1)));
+
+// ten bits spread to every third position: one axis of a 30-bit Morton code (the reference's KNN/simple_knn.cu:45-52)
+__device__ __forceinline__ unsigned morton_spread10(unsigned x) {
+    x = (x | (x << 16)) & 0x030000FF;
+    x = (x | (x << 8)) & 0x0300F00F;
+    x = (x | (x << 4)) & 0x030C30C3;
+    x = (x | (x << 2)) & 0x09249249;
+    return x;
+}
 
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 

@@ -14,10 +14,9 @@
 // prod_d |p_d - pos_d| / cube, and d/dgrid), so the whole DPSR stays differentiable w.r.t. points and normals.
 // Index / weight arithmetic follows the reference expression by expression (cube = 1 / res in fp32, floor(p / cube),
 // fmod(ceil(p / cube), res)), so cells and weights match it bit for bit; sums differ by atomic order only.
-#include "dgm_common.hpp"
+#include "dgm_host.hpp"
 
 namespace dgm {
-void set_last_error(const char* msg);  // c_api.hip
 
 struct Corner8 {
     int idx[8];
@@ -241,84 +240,73 @@ laplace_face_bwd_kernel(int F, int V, const int* __restrict__ f, const float* __
 
 using namespace dgm;
 
-namespace {
-int pfail(const char* m) {
-    dgm::set_last_error(m);
-    return 1;
-}
-int done() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : pfail(hipGetErrorString(e));
-}
-}  // namespace
-
 extern "C" {
 
 int dgm_dpsr_splat_forward(int n, int res, const float* V, const float* N, float* grid, void* stream) {
-    if (res <= 0 || res > 1024) return pfail("dpsr_splat_forward: bad resolution");
-    if (!grid) return pfail("dpsr_splat_forward: NULL pointer");
+    if (res <= 0 || res > 1024) return fail("dpsr_splat_forward: bad resolution");
+    if (!grid) return fail("dpsr_splat_forward: NULL pointer");
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(grid, 0, (size_t)3 * res * res * res * sizeof(float), st) != hipSuccess) return pfail("dpsr_splat_forward: memset failed");
+    if (hipMemsetAsync(grid, 0, (size_t)3 * res * res * res * sizeof(float), st) != hipSuccess) return fail("dpsr_splat_forward: memset failed");
     if (n <= 0) return 0;
-    if (!V || !N) return pfail("dpsr_splat_forward: NULL pointer");
+    if (!V || !N) return fail("dpsr_splat_forward: NULL pointer");
     hipLaunchKernelGGL(dpsr_splat_fwd_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, res, V, N, grid);
-    return done();
+    return launch_status();
 }
 
 int dgm_dpsr_splat_backward(int n, int res, const float* V, const float* N, const float* dgrid, float* dV, float* dN, void* stream) {
     if (n <= 0) return 0;
-    if (!V || !N || !dgrid || !dV || !dN) return pfail("dpsr_splat_backward: NULL pointer");
+    if (!V || !N || !dgrid || !dV || !dN) return fail("dpsr_splat_backward: NULL pointer");
     hipLaunchKernelGGL(dpsr_splat_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, res, V, N, dgrid, dV, dN);
-    return done();
+    return launch_status();
 }
 
 int dgm_dpsr_interp_forward(int n, int res, const float* phi, const float* V, float* fv, void* stream) {
     if (n <= 0) return 0;
-    if (!phi || !V || !fv) return pfail("dpsr_interp_forward: NULL pointer");
+    if (!phi || !V || !fv) return fail("dpsr_interp_forward: NULL pointer");
     hipLaunchKernelGGL(dpsr_interp_fwd_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, res, phi, V, fv);
-    return done();
+    return launch_status();
 }
 
 int dgm_dpsr_interp_backward(int n, int res, const float* phi, const float* V, const float* dfv, float* dphi, float* dV, void* stream) {
-    if (!dphi) return pfail("dpsr_interp_backward: NULL pointer");
+    if (!dphi) return fail("dpsr_interp_backward: NULL pointer");
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(dphi, 0, (size_t)res * res * res * sizeof(float), st) != hipSuccess) return pfail("dpsr_interp_backward: memset failed");
+    if (hipMemsetAsync(dphi, 0, (size_t)res * res * res * sizeof(float), st) != hipSuccess) return fail("dpsr_interp_backward: memset failed");
     if (n <= 0) return 0;
-    if (!phi || !V || !dfv || !dV) return pfail("dpsr_interp_backward: NULL pointer");
+    if (!phi || !V || !dfv || !dV) return fail("dpsr_interp_backward: NULL pointer");
     hipLaunchKernelGGL(dpsr_interp_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, res, phi, V, dfv, dphi, dV);
-    return done();
+    return launch_status();
 }
 
 int dgm_dpsr_spectral(int res, float sig, const float* in, float* out, int adjoint, void* stream) {
-    if (res <= 0 || !in || !out) return pfail("dpsr_spectral: bad argument");
+    if (res <= 0 || !in || !out) return fail("dpsr_spectral: bad argument");
     const size_t K = (size_t)res * res * (res / 2 + 1);
     hipLaunchKernelGGL(dpsr_spectral_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, res, sig,
                        (const float2*)in, (float2*)out, adjoint);
-    return done();
+    return launch_status();
 }
 
 size_t dgm_laplace_scratch_floats(int V) { return V > 0 ? (size_t)4 * V + (size_t)((V + 255) / 256) : 0; }
 
 int dgm_laplace_forward(int V, int F, const float* v_pos, const int* faces, float* scratch, float* loss, void* stream) {
-    if (V <= 0 || F < 0 || !v_pos || !scratch || !loss || (F > 0 && !faces)) return pfail("laplace_forward: bad argument");
+    if (V <= 0 || F < 0 || !v_pos || !scratch || !loss || (F > 0 && !faces)) return fail("laplace_forward: bad argument");
     hipStream_t st = (hipStream_t)stream;
     float *term = scratch, *norm = scratch + (size_t)3 * V, *partial = scratch + (size_t)4 * V;
-    if (hipMemsetAsync(scratch, 0, (size_t)4 * V * sizeof(float), st) != hipSuccess) return pfail("laplace_forward: memset failed");
+    if (hipMemsetAsync(scratch, 0, (size_t)4 * V * sizeof(float), st) != hipSuccess) return fail("laplace_forward: memset failed");
     const int nblk = (V + 255) / 256;
     if (F > 0) hipLaunchKernelGGL(laplace_face_fwd_kernel, dim3((F + 255) / 256), dim3(256), 0, st, F, v_pos, faces, term, norm);
     hipLaunchKernelGGL(laplace_vertex_kernel, dim3(nblk), dim3(256), 0, st, V, term, norm, partial);
     hipLaunchKernelGGL(laplace_sum_kernel, dim3(1), dim3(256), 0, st, nblk, V, partial, loss);
-    return done();
+    return launch_status();
 }
 
 int dgm_laplace_backward(int V, int F, const int* faces, const float* scratch, const float* dloss, float* dv, void* stream) {
-    if (V <= 0 || F < 0 || !scratch || !dloss || !dv || (F > 0 && !faces)) return pfail("laplace_backward: bad argument");
+    if (V <= 0 || F < 0 || !scratch || !dloss || !dv || (F > 0 && !faces)) return fail("laplace_backward: bad argument");
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(dv, 0, (size_t)3 * V * sizeof(float), st) != hipSuccess) return pfail("laplace_backward: memset failed");
+    if (hipMemsetAsync(dv, 0, (size_t)3 * V * sizeof(float), st) != hipSuccess) return fail("laplace_backward: memset failed");
     if (F > 0)
         hipLaunchKernelGGL(laplace_face_bwd_kernel, dim3((F + 255) / 256), dim3(256), 0, st, F, V, faces, scratch, scratch + (size_t)3 * V,
                            dloss, dv);
-    return done();
+    return launch_status();
 }
 
 }  // extern "C"

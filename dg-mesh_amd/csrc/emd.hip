@@ -199,7 +199,6 @@ emd_reduce_kernel(int n, int m, const float* __restrict__ rowcost, const float* 
     }
 }
 
-void set_last_error(const char* msg);
 
 }  // namespace dgm
 

@@ -8,10 +8,9 @@
 //    deformation network, columns [d_xyz 0:3 | d_rotation 3:7 | d_scaling 7:10 | ...].
 //  * cycle loss (R/train.py:221-238): (mean|b_xyz + d_xyz| + mean|b_rot + d_rot| + mean|b_scale + d_scale|) / 3 over
 //    the raw outputs of deform (a) and deform_back (b); two-level fixed-order reduction (deterministic).
-#include "dgm_common.hpp"
+#include "dgm_host.hpp"
 
 namespace dgm {
-void set_last_error(const char* msg);  // c_api.hip
 
 __global__ void __launch_bounds__(256)
 gaussian_apply_fwd_kernel(int P, const float* __restrict__ xyz, const float* __restrict__ scaling,
@@ -149,18 +148,6 @@ cycle_bwd_kernel(int N, const float* __restrict__ a, const float* __restrict__ b
 }  // namespace dgm
 
 using namespace dgm;
-
-namespace {
-int glue_fail(const char* m) {
-    dgm::set_last_error(m);
-    return 1;
-}
-int glue_done() {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return glue_fail(hipGetErrorString(e));
-    return 0;
-}
-}  // namespace
 
 // ---- 6-DoF deformation heads (is_6dof=True): screw motion -> rigid transform -> moved centres ------------------------------------
 // R/utils/time_utils.py:116-123 + R/utils/rigid_utils.py:10-83 (Modern Robotics 3.51 / 3.88) + the 6-DoF branch of render()
@@ -324,32 +311,32 @@ extern "C" {
 
 int dgm_se3_exp_forward(int N, const float* wv, int ld, float* T, void* stream) {
     if (N <= 0) return 0;
-    if (!wv || !T) return glue_fail("se3_exp_forward: NULL pointer");
-    if (ld < 6) return glue_fail("se3_exp_forward: rows need at least 6 columns (w, v)");
+    if (!wv || !T) return fail("se3_exp_forward: NULL pointer");
+    if (ld < 6) return fail("se3_exp_forward: rows need at least 6 columns (w, v)");
     hipLaunchKernelGGL(se3_exp_fwd_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, N, wv, ld, T);
-    return glue_done();
+    return launch_status();
 }
 
 int dgm_se3_exp_backward(int N, const float* wv, int ld, const float* dT, float* d_wv, int ldd, void* stream) {
     if (N <= 0) return 0;
-    if (!wv || !dT || !d_wv) return glue_fail("se3_exp_backward: NULL pointer");
-    if (ld < 6 || ldd < 6) return glue_fail("se3_exp_backward: rows need at least 6 columns (w, v)");
+    if (!wv || !dT || !d_wv) return fail("se3_exp_backward: NULL pointer");
+    if (ld < 6 || ldd < 6) return fail("se3_exp_backward: rows need at least 6 columns (w, v)");
     hipLaunchKernelGGL(se3_exp_bwd_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, N, wv, ld, dT, d_wv, ldd);
-    return glue_done();
+    return launch_status();
 }
 
 int dgm_se3_transform_forward(int N, const float* T, const float* xyz, float* out, void* stream) {
     if (N <= 0) return 0;
-    if (!T || !xyz || !out) return glue_fail("se3_transform_forward: NULL pointer");
+    if (!T || !xyz || !out) return fail("se3_transform_forward: NULL pointer");
     hipLaunchKernelGGL(se3_transform_fwd_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, N, T, xyz, out);
-    return glue_done();
+    return launch_status();
 }
 
 int dgm_se3_transform_backward(int N, const float* T, const float* xyz, const float* g_out, float* dT, float* d_xyz, void* stream) {
     if (N <= 0) return 0;
-    if (!T || !xyz || !g_out || !dT || !d_xyz) return glue_fail("se3_transform_backward: NULL pointer");
+    if (!T || !xyz || !g_out || !dT || !d_xyz) return fail("se3_transform_backward: NULL pointer");
     hipLaunchKernelGGL(se3_transform_bwd_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, N, T, xyz, g_out, dT, d_xyz);
-    return glue_done();
+    return launch_status();
 }
 
 int dgm_gaussian_apply_forward(int P, const float* xyz, const float* scaling, const float* rotation, const float* opacity,
@@ -357,11 +344,11 @@ int dgm_gaussian_apply_forward(int P, const float* xyz, const float* scaling, co
                                void* stream) {
     if (P <= 0) return 0;
     if (!xyz || !scaling || !rotation || !opacity || !delta || !means3D || !scales || !rotations || !opacities)
-        return glue_fail("gaussian_apply_forward: NULL pointer");
-    if (ld < 10) return glue_fail("gaussian_apply_forward: delta needs at least 10 columns (d_xyz, d_rotation, d_scaling)");
+        return fail("gaussian_apply_forward: NULL pointer");
+    if (ld < 10) return fail("gaussian_apply_forward: delta needs at least 10 columns (d_xyz, d_rotation, d_scaling)");
     hipLaunchKernelGGL(gaussian_apply_fwd_kernel, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, xyz, scaling,
                        rotation, opacity, delta, ld, means3D, scales, rotations, opacities);
-    return glue_done();
+    return launch_status();
 }
 
 int dgm_gaussian_apply_backward(int P, const float* scaling, const float* rotation, const float* opacity,
@@ -371,33 +358,33 @@ int dgm_gaussian_apply_backward(int P, const float* scaling, const float* rotati
     if (P <= 0) return 0;
     if (!scaling || !rotation || !opacity || !g_means3D || !g_scales || !g_rotations || !g_opacities || !d_xyz || !d_scaling ||
         !d_rotation || !d_opacity || !d_delta)
-        return glue_fail("gaussian_apply_backward: NULL pointer");
-    if (ld < 10) return glue_fail("gaussian_apply_backward: delta needs at least 10 columns");
+        return fail("gaussian_apply_backward: NULL pointer");
+    if (ld < 10) return fail("gaussian_apply_backward: delta needs at least 10 columns");
     hipLaunchKernelGGL(gaussian_apply_bwd_kernel, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, scaling, rotation,
                        opacity, g_means3D, g_scales, g_rotations, g_opacities, d_xyz, d_scaling, d_rotation, d_opacity, d_delta,
                        ld);
-    return glue_done();
+    return launch_status();
 }
 
 size_t dgm_cycle_loss_workspace_bytes(int N) { return (size_t)((N + CYC_ROWS - 1) / CYC_ROWS + 1) * 3 * sizeof(float); }
 
 int dgm_cycle_loss_forward(int N, const float* a, const float* b, int ld, char* workspace, float* out, void* stream) {
-    if (N <= 0) return glue_fail("cycle_loss_forward: N must be positive");
-    if (!a || !b || !workspace || !out) return glue_fail("cycle_loss_forward: NULL pointer");
-    if (ld < 10) return glue_fail("cycle_loss_forward: needs at least 10 columns");
+    if (N <= 0) return fail("cycle_loss_forward: N must be positive");
+    if (!a || !b || !workspace || !out) return fail("cycle_loss_forward: NULL pointer");
+    if (ld < 10) return fail("cycle_loss_forward: needs at least 10 columns");
     const int blocks = (N + CYC_ROWS - 1) / CYC_ROWS;
     hipLaunchKernelGGL(cycle_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, N, a, b, ld, (float*)workspace);
     hipLaunchKernelGGL(cycle_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, N, blocks, (const float*)workspace, out);
-    return glue_done();
+    return launch_status();
 }
 
 int dgm_cycle_loss_backward(int N, const float* a, const float* b, int ld, const float* grad_out, float* d_a, float* d_b,
                             void* stream) {
     if (N <= 0) return 0;
-    if (!a || !b || !grad_out || !d_a || !d_b) return glue_fail("cycle_loss_backward: NULL pointer");
+    if (!a || !b || !grad_out || !d_a || !d_b) return fail("cycle_loss_backward: NULL pointer");
     hipLaunchKernelGGL(cycle_bwd_kernel, dim3((unsigned)(((size_t)N * ld + 255) / 256)), dim3(256), 0, (hipStream_t)stream, N, a, b, ld,
                        grad_out, d_a, d_b);
-    return glue_done();
+    return launch_status();
 }
 
 }  // extern "C"

@@ -27,7 +27,6 @@
 
 namespace dgm {
 
-void set_last_error(const char* msg);  // c_api.hip
 
 static constexpr int UF_ROWS = 1024;  // rows per band = threads per workgroup
 static constexpr int UF_WAVES = UF_ROWS / 64;

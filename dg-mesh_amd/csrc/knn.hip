@@ -20,18 +20,8 @@
 
 namespace dgm {
 
-void launch_scan_blocks(hipStream_t st, int n, const unsigned* in, unsigned* out, unsigned* total);
-
 static constexpr int KNN_BOX = 256;
 static constexpr int RS_TILE = 2048;  // keys per radix-sort workgroup
-
-__device__ __forceinline__ unsigned prep_morton(unsigned x) {  // KNN/simple_knn.cu:45-52
-    x = (x | (x << 16)) & 0x030000FF;
-    x = (x | (x << 8)) & 0x0300F00F;
-    x = (x | (x << 4)) & 0x030C30C3;
-    x = (x | (x << 2)) & 0x09249249;
-    return x;
-}
 
 // stage 1: partial bounding boxes (both reductions start from 0 like the reference, simple_knn.cu:191-199)
 __global__ void __launch_bounds__(256)
@@ -82,7 +72,7 @@ __global__ void knn_morton_kernel(int P, const float* __restrict__ pts, const fl
 #pragma unroll
     for (int a = 0; a < 3; a++) {  // KNN/simple_knn.cu:54-61
         const float mn = bbox[a], mx = bbox[3 + a];
-        c[a] = prep_morton(f2u_sat(((pts[3 * i + a] - mn) / (mx - mn)) * ((1 << 10) - 1)));
+        c[a] = morton_spread10(f2u_sat(((pts[3 * i + a] - mn) / (mx - mn)) * ((1 << 10) - 1)));
     }
     codes[i] = c[0] | (c[1] << 1) | (c[2] << 2);
     idx[i] = (unsigned)i;

@@ -225,10 +225,6 @@ loss_bwd_kernel(const Gauss11 gw, const float* __restrict__ I, const float* __re
 }  // namespace dgm
 
 using namespace dgm;
-namespace dgm {
-void set_last_error(const char* msg);
-}
-
 extern "C" {
 
 size_t dgm_image_loss_workspace_bytes(int channels, int H, int W) {

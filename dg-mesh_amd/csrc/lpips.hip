@@ -278,7 +278,6 @@ static bool lpips_plan(int net, int B, int H, int W, LpPlan* P) {
     return true;
 }
 
-void set_last_error(const char* msg);
 
 }  // namespace dgm
 

@@ -13,12 +13,8 @@
 //     vid(q, axis) = voff[q / 64] + popcount of the crossed bits of the word's lanes below q + crossed lower axes of q itself.
 // Those 0.5 B of ballots + 8 B of offsets per 64 points are the edge-to-vertex map the backward gathers through: each point sums
 // the terms of its <= 6 incident crossed edges in a fixed order (own x, y, z, then incoming x, y, z), so dgrid is bit-reproducible.
-#include "dgm_common.hpp"
+#include "dgm_host.hpp"
 #include "mc_tables.hpp"
-
-namespace dgm {
-void set_last_error(const char* msg);  // c_api.hip
-}
 
 using namespace dgm;
 
@@ -332,14 +328,6 @@ mc_backward_kernel(McDims d, const float* __restrict__ g, const float* __restric
     }
 }
 
-int mfail(const char* m) {
-    dgm::set_last_error(m);
-    return 1;
-}
-int mdone() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : mfail(hipGetErrorString(e));
-}
 
 // dims >= 2 and every vertex id / triangle count within int32 (at most 3 vertices per point, 5 triangles per cell)
 bool mc_dims(int X, int Y, int Z, McDims& d) {
@@ -361,22 +349,22 @@ size_t dgm_mc_scratch_bytes(int X, int Y, int Z) {
 
 int dgm_mc_count(int X, int Y, int Z, const float* grid, float iso, char* scratch, int* counts, void* stream) {
     McDims d;
-    if (!mc_dims(X, Y, Z, d)) return mfail("mc_count: every dimension must be >= 2 and 5 * X * Y * Z must fit in int32");
-    if (!grid || !scratch || !counts) return mfail("mc_count: NULL pointer");
+    if (!mc_dims(X, Y, Z, d)) return fail("mc_count: every dimension must be >= 2 and 5 * X * Y * Z must fit in int32");
+    if (!grid || !scratch || !counts) return fail("mc_count: NULL pointer");
     const McLayout L = mc_layout(d.N);
     hipStream_t st = (hipStream_t)stream;
     const int NB = (int)((d.N + MC_PTS - 1) / MC_PTS);
     hipLaunchKernelGGL(mc_count_kernel, dim3(NB), dim3(MC_THREADS), 0, st, d, grid, iso, (McWord*)(scratch + L.words),
                        (uint2*)(scratch + L.wcnt), (uint2*)(scratch + L.blk));
     hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(MC_SCAN_THREADS), 0, st, NB, (uint2*)(scratch + L.blk), counts);
-    return mdone();
+    return launch_status();
 }
 
 int dgm_mc_emit(int X, int Y, int Z, const float* grid, const float* deform, float iso, int normalize, char* scratch, int V, int F,
                 float* verts, int* faces, void* stream) {
     McDims d;
-    if (!mc_dims(X, Y, Z, d)) return mfail("mc_emit: every dimension must be >= 2 and 5 * X * Y * Z must fit in int32");
-    if (!grid || !scratch || V < 0 || F < 0 || (V > 0 && !verts) || (F > 0 && !faces)) return mfail("mc_emit: NULL pointer or bad count");
+    if (!mc_dims(X, Y, Z, d)) return fail("mc_emit: every dimension must be >= 2 and 5 * X * Y * Z must fit in int32");
+    if (!grid || !scratch || V < 0 || F < 0 || (V > 0 && !verts) || (F > 0 && !faces)) return fail("mc_emit: NULL pointer or bad count");
     const McLayout L = mc_layout(d.N);
     hipStream_t st = (hipStream_t)stream;
     const int NB = (int)((d.N + MC_PTS - 1) / MC_PTS);
@@ -388,21 +376,21 @@ int dgm_mc_emit(int X, int Y, int Z, const float* grid, const float* deform, flo
     if (F > 0)
         hipLaunchKernelGGL(mc_emit_faces_kernel, dim3((unsigned)((d.N + MC_THREADS - 1) / MC_THREADS)), dim3(MC_THREADS), 0, st, d,
                            words, voff, foff, F, faces);
-    return mdone();
+    return launch_status();
 }
 
 int dgm_mc_backward(int X, int Y, int Z, const float* grid, const float* deform, float iso, int normalize, const char* scratch, int V,
                     const float* dverts, float* dgrid, float* ddeform, void* stream) {
     McDims d;
-    if (!mc_dims(X, Y, Z, d)) return mfail("mc_backward: every dimension must be >= 2 and 5 * X * Y * Z must fit in int32");
+    if (!mc_dims(X, Y, Z, d)) return fail("mc_backward: every dimension must be >= 2 and 5 * X * Y * Z must fit in int32");
     if (!grid || !scratch || !dgrid || V < 0 || (V > 0 && !dverts) || (!deform != !ddeform))
-        return mfail("mc_backward: NULL pointer or bad count");
+        return fail("mc_backward: NULL pointer or bad count");
     const McLayout L = mc_layout(d.N);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(mc_backward_kernel, dim3((unsigned)((d.N + MC_THREADS - 1) / MC_THREADS)), dim3(MC_THREADS), 0, st, d, grid,
                        deform, iso, normalize, (const McWord*)(scratch + L.words), (const unsigned*)(scratch + L.voff), V, dverts,
                        dgrid, ddeform);
-    return mdone();
+    return launch_status();
 }
 
 }  // extern "C"

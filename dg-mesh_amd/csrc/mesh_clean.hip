@@ -30,13 +30,10 @@
 #include <float.h>
 #include <math.h>
 
-#include "dgm_common.hpp"
+#include "dgm_host.hpp"
+#include "mesh_scan.hpp"
 
 #pragma clang fp contract(off)
-
-namespace dgm {
-void set_last_error(const char* msg);
-}  // namespace dgm
 
 namespace {
 using namespace dgm;
@@ -45,19 +42,11 @@ constexpr int MC_THREADS = 256;
 constexpr int MC_ITEMS = 16;                        // consecutive integers per thread
 constexpr int MC_TILE = MC_THREADS * MC_ITEMS;      // integers per workgroup: the fixed partition of every scan here
 constexpr int MC_WAVES = MC_THREADS / 64;
+static_assert(MC_ITEMS == SCAN_ITEMS && MC_WAVES == SCAN_WAVES, "the compaction kernels use the tile prefix of mesh_scan.hpp");
 constexpr int SEL_MAX_BLOCKS = 1024;
 
-unsigned blocks(long long n, int t = MC_THREADS) { return (unsigned)((n + t - 1) / t); }
 int tiles(long long n) { return (int)((n + MC_TILE - 1) / MC_TILE); }
 
-int mfail(const char* m) {
-    set_last_error(m);
-    return 1;
-}
-int mdone() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : mfail(hipGetErrorString(e));
-}
 
 #define AGENT __HIP_MEMORY_SCOPE_AGENT
 
@@ -392,40 +381,21 @@ compact_mark_kernel(int V, int F, const int* __restrict__ faces, const unsigned 
     if (k) vert_flag[a] = 1, vert_flag[b] = 1, vert_flag[c] = 1;  // (racing stores of one value)
 }
 
-// The 16 flags of this thread (0 behind n), its exclusive prefix inside the tile and the tile's total.
-__device__ __forceinline__ unsigned tile_prefix(long long n, const int* __restrict__ flag, long long base, unsigned* fl, unsigned* lds,
-                                                unsigned& total) {
-    unsigned s = 0;
-#pragma unroll
-    for (int k = 0; k < MC_ITEMS; k++) {
-        fl[k] = base + k < n ? (flag[base + k] != 0 ? 1u : 0u) : 0u;
-        s += fl[k];
-    }
-    const unsigned inc = wave_inclusive_scan_u32(s);
-    const int wv = threadIdx.x >> 6;
-    if (lane_id() == 63) lds[wv] = inc;
-    __syncthreads();
-    unsigned before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < MC_WAVES; w++) {
-        const unsigned t = lds[w];
-        if (w < wv) before += t;
-        all += t;
-    }
-    __syncthreads();
-    total = all;
-    return before + inc - s;
-}
+// a set flag counts 1 in the shared tile prefix (mesh_scan.hpp)
+struct FlagLoad {
+    const int* flag;
+    __device__ void operator()(long long i, unsigned* x) const { x[0] = flag[i] != 0 ? 1u : 0u; }
+};
 
 // blocks [0, nbV) take the vertex flags, the others the face flags
 __global__ void __launch_bounds__(MC_THREADS)
 scan_totals_kernel(long long nV, const int* __restrict__ vflag, int nbV, long long nF, const int* __restrict__ fflag,
                    unsigned* __restrict__ tile_total) {
-    __shared__ unsigned lds[MC_WAVES];
+    __shared__ unsigned lds[MC_WAVES][1];
     const bool isV = (int)blockIdx.x < nbV;
     const long long tile = isV ? blockIdx.x : blockIdx.x - nbV;
-    unsigned fl[MC_ITEMS], total;
-    tile_prefix(isV ? nV : nF, isV ? vflag : fflag, tile * MC_TILE + (long long)threadIdx.x * MC_ITEMS, fl, lds, total);
+    unsigned fl[MC_ITEMS][1], pre, total;
+    scan_tile_prefix<1>(isV ? nV : nF, FlagLoad{isV ? vflag : fflag}, tile * MC_TILE + (long long)threadIdx.x * MC_ITEMS, fl, lds, &pre, &total);
     if (threadIdx.x == 0) tile_total[blockIdx.x] = total;
 }
 
@@ -459,16 +429,17 @@ scan_offsets_kernel(int nbV, int nbF, const unsigned* __restrict__ tile_total, u
 __global__ void __launch_bounds__(MC_THREADS)
 emit_verts_kernel(long long V, int Vn, const float* __restrict__ verts, const int* __restrict__ vflag, const unsigned* __restrict__ tile_off,
                   int* __restrict__ vert_new, float* __restrict__ verts_out, int* __restrict__ vert_index) {
-    __shared__ unsigned lds[MC_WAVES];
-    unsigned fl[MC_ITEMS], total;
+    __shared__ unsigned lds[MC_WAVES][1];
+    unsigned fl[MC_ITEMS][1], at, total;
     const long long base = (long long)blockIdx.x * MC_TILE + (long long)threadIdx.x * MC_ITEMS;
-    unsigned at = tile_off[blockIdx.x] + tile_prefix(V, vflag, base, fl, lds, total);
+    scan_tile_prefix<1>(V, FlagLoad{vflag}, base, fl, lds, &at, &total);
+    at += tile_off[blockIdx.x];
 #pragma unroll
     for (int k = 0; k < MC_ITEMS; k++) {
         const long long v = base + k;
         if (v >= V) break;
         vert_new[v] = (int)at;
-        if (fl[k]) {
+        if (fl[k][0]) {
             if (at < (unsigned)Vn) {  // (Vn is the count this scan produced; the test keeps a wrong Vn inside the outputs)
 #pragma unroll
                 for (int a = 0; a < 3; a++) verts_out[3 * (long long)at + a] = verts[3 * v + a];
@@ -482,15 +453,16 @@ emit_verts_kernel(long long V, int Vn, const float* __restrict__ verts, const in
 __global__ void __launch_bounds__(MC_THREADS)
 emit_faces_kernel(long long F, int Fn, const int* __restrict__ faces, const int* __restrict__ fflag, const unsigned* __restrict__ tile_off,
                   const int* __restrict__ vert_new, int* __restrict__ faces_out, int* __restrict__ face_index) {
-    __shared__ unsigned lds[MC_WAVES];
-    unsigned fl[MC_ITEMS], total;
+    __shared__ unsigned lds[MC_WAVES][1];
+    unsigned fl[MC_ITEMS][1], at, total;
     const long long base = (long long)blockIdx.x * MC_TILE + (long long)threadIdx.x * MC_ITEMS;
-    unsigned at = tile_off[blockIdx.x] + tile_prefix(F, fflag, base, fl, lds, total);
+    scan_tile_prefix<1>(F, FlagLoad{fflag}, base, fl, lds, &at, &total);
+    at += tile_off[blockIdx.x];
 #pragma unroll
     for (int k = 0; k < MC_ITEMS; k++) {
         const long long f = base + k;
         if (f >= F) break;
-        if (fl[k]) {
+        if (fl[k][0]) {
             if (at < (unsigned)Fn) {  // (a set flag says that the three indices are inside vert_new)
 #pragma unroll
                 for (int a = 0; a < 3; a++) faces_out[3 * (long long)at + a] = vert_new[faces[3 * f + a]];
@@ -538,28 +510,28 @@ size_t dgm_mesh_cc_scratch_bytes(int V, int F) {
 }
 
 int dgm_mesh_cc_label(int V, int F, const int* faces, char* scratch, int* labels, int* info, void* stream) {
-    if (V < 0 || F < 0) return mfail("mesh_cc_label: need V >= 0 and F >= 0");
-    if (!info || !scratch || (V > 0 && !labels) || (F > 0 && !faces)) return mfail("mesh_cc_label: NULL pointer");
+    if (V < 0 || F < 0) return fail("mesh_cc_label: need V >= 0 and F >= 0");
+    if (!info || !scratch || (V > 0 && !labels) || (F > 0 && !faces)) return fail("mesh_cc_label: NULL pointer");
     hipStream_t st = (hipStream_t)stream;
     int* parent = (int*)align_ptr(scratch);
     hipLaunchKernelGGL(cc_init_kernel, dim3(blocks(V > 2 ? V : 2)), dim3(MC_THREADS), 0, st, V, parent, info);
     if (F > 0) hipLaunchKernelGGL(cc_hook_kernel, dim3(blocks(F)), dim3(MC_THREADS), 0, st, V, F, faces, parent, info);
     if (V > 0) hipLaunchKernelGGL(cc_label_kernel, dim3(blocks(V)), dim3(MC_THREADS), 0, st, V, (const int*)parent, labels);
-    return mdone();
+    return launch_status();
 }
 
 int dgm_mesh_cc_stats(int V, int F, const float* verts, const int* faces, const int* labels, int* comp_faces, int* comp_verts,
                       float* comp_bbox, void* stream) {
-    if (V < 0 || F < 0) return mfail("mesh_cc_stats: need V >= 0 and F >= 0");
+    if (V < 0 || F < 0) return fail("mesh_cc_stats: need V >= 0 and F >= 0");
     if (V == 0) return 0;
-    if (!verts || !labels || !comp_faces || !comp_verts || !comp_bbox || (F > 0 && !faces)) return mfail("mesh_cc_stats: NULL pointer");
+    if (!verts || !labels || !comp_faces || !comp_verts || !comp_bbox || (F > 0 && !faces)) return fail("mesh_cc_stats: NULL pointer");
     hipStream_t st = (hipStream_t)stream;
     unsigned* box = (unsigned*)comp_bbox;
     hipLaunchKernelGGL(stats_init_kernel, dim3(blocks(V)), dim3(MC_THREADS), 0, st, V, comp_faces, comp_verts, box);
     hipLaunchKernelGGL(stats_vert_kernel, dim3(tiles(V)), dim3(MC_THREADS), 0, st, V, verts, labels, comp_verts, box);
     if (F > 0) hipLaunchKernelGGL(stats_face_kernel, dim3(tiles(F)), dim3(MC_THREADS), 0, st, V, F, faces, labels, comp_faces);
     hipLaunchKernelGGL(stats_decode_kernel, dim3(blocks(V)), dim3(MC_THREADS), 0, st, V, (const int*)comp_verts, box);
-    return mdone();
+    return launch_status();
 }
 
 size_t dgm_mesh_cc_select_scratch_bytes(void) { return 256 + 64; }
@@ -567,11 +539,11 @@ size_t dgm_mesh_cc_select_scratch_bytes(void) { return 256 + 64; }
 int dgm_mesh_cc_select(int V, int F, const int* faces, const int* labels, const int* comp_faces, const int* comp_verts,
                        const float* comp_bbox, int largest, int min_faces, float min_diameter_frac, char* scratch, unsigned char* keep,
                        void* stream) {
-    if (V < 0 || F < 0) return mfail("mesh_cc_select: need V >= 0 and F >= 0");
-    if (!(min_diameter_frac >= 0.f) || min_faces < 0) return mfail("mesh_cc_select: need min_faces >= 0 and min_diameter_frac >= 0");
+    if (V < 0 || F < 0) return fail("mesh_cc_select: need V >= 0 and F >= 0");
+    if (!(min_diameter_frac >= 0.f) || min_faces < 0) return fail("mesh_cc_select: need min_faces >= 0 and min_diameter_frac >= 0");
     if (F == 0) return 0;
     if (!faces || !keep || !scratch || (V > 0 && (!labels || !comp_faces || !comp_verts || !comp_bbox)))
-        return mfail("mesh_cc_select: NULL pointer");
+        return fail("mesh_cc_select: NULL pointer");
     hipStream_t st = (hipStream_t)stream;
     unsigned* sel = (unsigned*)align_ptr(scratch);
     hipLaunchKernelGGL(sel_init_kernel, dim3(1), dim3(64), 0, st, sel);
@@ -582,7 +554,7 @@ int dgm_mesh_cc_select(int V, int F, const int* faces, const int* labels, const 
     }
     hipLaunchKernelGGL(sel_keep_kernel, dim3(blocks(F)), dim3(MC_THREADS), 0, st, V, F, faces, labels, comp_faces, comp_bbox,
                        largest ? 1 : 0, min_faces, min_diameter_frac, (const unsigned*)sel, keep);
-    return mdone();
+    return launch_status();
 }
 
 size_t dgm_mesh_compact_scratch_bytes(int V, int F) {
@@ -591,26 +563,26 @@ size_t dgm_mesh_compact_scratch_bytes(int V, int F) {
 }
 
 int dgm_mesh_compact_count(int V, int F, const int* faces, const unsigned char* keep, char* scratch, int* counts, void* stream) {
-    if (V < 0 || F < 0) return mfail("mesh_compact_count: need V >= 0 and F >= 0");
-    if (!scratch || !counts || (F > 0 && (!faces || !keep))) return mfail("mesh_compact_count: NULL pointer");
+    if (V < 0 || F < 0) return fail("mesh_compact_count: need V >= 0 and F >= 0");
+    if (!scratch || !counts || (F > 0 && (!faces || !keep))) return fail("mesh_compact_count: NULL pointer");
     hipStream_t st = (hipStream_t)stream;
     const CompactScratch s = compact_layout(scratch, V, F);
     const int nbV = tiles(V), nbF = tiles(F);
-    if (V > 0 && hipMemsetAsync(s.vert_flag, 0, (size_t)V * 4, st) != hipSuccess) return mdone();
+    if (V > 0 && hipMemsetAsync(s.vert_flag, 0, (size_t)V * 4, st) != hipSuccess) return launch_status();
     if (F > 0) hipLaunchKernelGGL(compact_mark_kernel, dim3(blocks(F)), dim3(MC_THREADS), 0, st, V, F, faces, keep, s.vert_flag, s.face_flag);
     if (nbV + nbF > 0)
         hipLaunchKernelGGL(scan_totals_kernel, dim3(nbV + nbF), dim3(MC_THREADS), 0, st, (long long)V, (const int*)s.vert_flag, nbV,
                            (long long)F, (const int*)s.face_flag, s.tile_total);
     hipLaunchKernelGGL(scan_offsets_kernel, dim3(2), dim3(MC_THREADS), 0, st, nbV, nbF, (const unsigned*)s.tile_total, s.tile_off, counts);
-    return mdone();
+    return launch_status();
 }
 
 int dgm_mesh_compact_emit(int V, int F, const float* verts, const int* faces, char* scratch, int Vn, int Fn, float* verts_out,
                           int* faces_out, int* vert_index, int* face_index, void* stream) {
-    if (V < 0 || F < 0 || Vn < 0 || Fn < 0 || Vn > V || Fn > F) return mfail("mesh_compact_emit: need 0 <= Vn <= V and 0 <= Fn <= F");
+    if (V < 0 || F < 0 || Vn < 0 || Fn < 0 || Vn > V || Fn > F) return fail("mesh_compact_emit: need 0 <= Vn <= V and 0 <= Fn <= F");
     if (!scratch || (V > 0 && !verts) || (F > 0 && !faces) || (Vn > 0 && (!verts_out || !vert_index)) ||
         (Fn > 0 && (!faces_out || !face_index)))
-        return mfail("mesh_compact_emit: NULL pointer");
+        return fail("mesh_compact_emit: NULL pointer");
     hipStream_t st = (hipStream_t)stream;
     const CompactScratch s = compact_layout(scratch, V, F);
     const int nbV = tiles(V), nbF = tiles(F);
@@ -620,7 +592,7 @@ int dgm_mesh_compact_emit(int V, int F, const float* verts, const int* faces, ch
     if (nbF > 0)
         hipLaunchKernelGGL(emit_faces_kernel, dim3(nbF), dim3(MC_THREADS), 0, st, (long long)F, Fn, faces, (const int*)s.face_flag,
                            (const unsigned*)s.tile_off + nbV, (const int*)s.vert_new, faces_out, face_index);
-    return mdone();
+    return launch_status();
 }
 
 }  // extern "C"

@@ -29,14 +29,10 @@
 #include <math.h>
 #include <stdio.h>
 
-#include "dgm_common.hpp"
+#include "dgm_host.hpp"
 #include "mesh_scan.hpp"
 
 #pragma clang fp contract(off)
-
-namespace dgm {
-void set_last_error(const char* msg);
-}  // namespace dgm
 
 namespace {
 using namespace dgm;
@@ -50,16 +46,7 @@ constexpr int ME_SUMS = 5;             // sums per workgroup: boundary, non-mani
 // the class of an edge from its faces per direction
 constexpr int KIND_REGULAR = 0, KIND_BOUNDARY = 1, KIND_NONMANIFOLD = 2, KIND_MISORIENTED = 3;
 
-unsigned blocks(long long n, int t = ME_THREADS) { return (unsigned)((n + t - 1) / t); }
 
-int efail(const char* m) {
-    set_last_error(m);
-    return 1;
-}
-int edone() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : efail(hipGetErrorString(e));
-}
 
 __device__ __forceinline__ bool valid_face(int V, int a, int b, int c) {
     return a >= 0 && a < V && b >= 0 && b < V && c >= 0 && c < V && a != b && b != c && a != c;
@@ -328,11 +315,11 @@ int check_sizes(const char* who, int V, int F) {
     static thread_local char msg[160];
     if (V < 0 || F < 0) {
         snprintf(msg, sizeof msg, "%s: need V >= 0 and F >= 0", who);
-        return efail(msg);
+        return fail(msg);
     }
     if (F > ME_MAX_FACES) {
         snprintf(msg, sizeof msg, "%s: F = %d is over the supported %d faces", who, F, ME_MAX_FACES);
-        return efail(msg);
+        return fail(msg);
     }
     return 0;
 }
@@ -348,16 +335,16 @@ size_t dgm_mesh_edges_scratch_bytes(int V, int F) {
 
 int dgm_mesh_edges_count(int V, int F, const int* faces, char* scratch, int* adj_offset, unsigned char* vert_flag, int* info, void* stream) {
     if (check_sizes("mesh_edges_count", V, F)) return 1;
-    if (!scratch || !adj_offset || !info || (V > 0 && !vert_flag) || (F > 0 && !faces)) return efail("mesh_edges_count: NULL pointer");
+    if (!scratch || !adj_offset || !info || (V > 0 && !vert_flag) || (F > 0 && !faces)) return fail("mesh_edges_count: NULL pointer");
     hipStream_t st = (hipStream_t)stream;
     if (V == 0) {  // no vertex: no valid face
-        if (hipMemsetAsync(info, 0, ME_INFO * 4, st) != hipSuccess || hipMemsetAsync(adj_offset, 0, 4, st) != hipSuccess) return edone();
-        return edone();
+        if (hipMemsetAsync(info, 0, ME_INFO * 4, st) != hipSuccess || hipMemsetAsync(adj_offset, 0, 4, st) != hipSuccess) return launch_status();
+        return launch_status();
     }
     const EdgesScratch s = edges_layout(scratch, V, F);
-    if (hipMemsetAsync(s.count, 0, (size_t)V * 4, st) != hipSuccess) return edone();
+    if (hipMemsetAsync(s.count, 0, (size_t)V * 4, st) != hipSuccess) return launch_status();
     if (F > 0) hipLaunchKernelGGL(me_count_kernel, dim3(blocks(F)), dim3(ME_THREADS), 0, st, V, F, faces, s.count);
-    scan_exclusive(st, (long long)V, (const unsigned*)s.count, s.tile_total, s.tile_off, s.offset, s.cursor, s.ctl);
+    scan_exclusive(st, (long long)V, (const unsigned*)s.count, s.tile_total, s.tile_off, s.offset, s.cursor, false, s.ctl);
     if (F > 0) {
         hipLaunchKernelGGL(me_fill_kernel, dim3(blocks(F)), dim3(ME_THREADS), 0, st, V, F, faces, (const unsigned*)s.offset, s.cursor,
                            6ull * (unsigned long long)F, s.raw, s.owner);
@@ -367,39 +354,39 @@ int dgm_mesh_edges_count(int V, int F, const int* faces, char* scratch, int* adj
     hipLaunchKernelGGL(me_degree_kernel, dim3(blocks(V)), dim3(ME_THREADS), 0, st, V, (const unsigned long long*)s.sorted,
                        (const unsigned*)s.offset, (const unsigned*)s.count, s.deg, s.updeg, vert_flag, s.partial);
     // (2 E <= 6 F < 2^31: the offsets are the same numbers as int32)
-    scan_exclusive(st, (long long)V, (const unsigned*)s.deg, s.tile_total, s.tile_off, (unsigned*)adj_offset, nullptr, (unsigned*)adj_offset + V);
-    scan_exclusive(st, (long long)V, (const unsigned*)s.updeg, s.tile_total, s.tile_off, s.edge_offset, nullptr, s.ctl + 1);
+    scan_exclusive(st, (long long)V, (const unsigned*)s.deg, s.tile_total, s.tile_off, (unsigned*)adj_offset, nullptr, false, (unsigned*)adj_offset + V);
+    scan_exclusive(st, (long long)V, (const unsigned*)s.updeg, s.tile_total, s.tile_off, s.edge_offset, nullptr, false, s.ctl + 1);
     hipLaunchKernelGGL(me_info_kernel, dim3(1), dim3(ME_THREADS), 0, st, (int)blocks(V), (const unsigned*)s.partial, (const unsigned*)s.ctl,
                        (const int*)adj_offset + V, info);
-    return edone();
+    return launch_status();
 }
 
 int dgm_mesh_edges_emit(int V, int F, char* scratch, int E, const int* adj_offset, int* adj, unsigned char* adj_kind, int* edges,
                         int* edge_faces, int* edge_count, void* stream) {
     if (check_sizes("mesh_edges_emit", V, F)) return 1;
-    if (E < 0 || (long long)E > 3ll * F) return efail("mesh_edges_emit: need 0 <= E <= 3 F");
-    if (!scratch || !adj_offset) return efail("mesh_edges_emit: NULL pointer");
+    if (E < 0 || (long long)E > 3ll * F) return fail("mesh_edges_emit: need 0 <= E <= 3 F");
+    if (!scratch || !adj_offset) return fail("mesh_edges_emit: NULL pointer");
     if (V == 0 || E == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const EdgesScratch s = edges_layout(scratch, V, F);
     hipLaunchKernelGGL(me_emit_kernel, dim3(blocks(V)), dim3(ME_THREADS), 0, st, V, E, (const unsigned long long*)s.sorted,
                        (const unsigned*)s.offset, (const unsigned*)s.count, adj_offset, (const unsigned*)s.edge_offset, adj, adj_kind, edges,
                        edge_faces, edge_count);
-    return edone();
+    return launch_status();
 }
 
 int dgm_mesh_smooth_step(int V, int A, const float* verts_in, const int* adj_offset, const int* adj, const unsigned char* adj_kind,
                          const unsigned char* vert_flag, double factor, int boundary, float* verts_out, void* stream) {
-    if (V < 0 || A < 0) return efail("mesh_smooth_step: need V >= 0 and A >= 0");
-    if (boundary < 0 || boundary > 2) return efail("mesh_smooth_step: boundary must be 0 (fixed), 1 (curve) or 2 (free)");
-    if (!(factor == factor) || fabs(factor) > DBL_MAX) return efail("mesh_smooth_step: need a finite factor");
+    if (V < 0 || A < 0) return fail("mesh_smooth_step: need V >= 0 and A >= 0");
+    if (boundary < 0 || boundary > 2) return fail("mesh_smooth_step: boundary must be 0 (fixed), 1 (curve) or 2 (free)");
+    if (!(factor == factor) || fabs(factor) > DBL_MAX) return fail("mesh_smooth_step: need a finite factor");
     if (V == 0) return 0;
     if (!verts_in || !verts_out || !adj_offset || !vert_flag || (A > 0 && (!adj || (boundary == 1 && !adj_kind))))
-        return efail("mesh_smooth_step: NULL pointer");
-    if (verts_in == verts_out) return efail("mesh_smooth_step: verts_out must not be verts_in (every vertex reads its neighbours' old positions)");
+        return fail("mesh_smooth_step: NULL pointer");
+    if (verts_in == verts_out) return fail("mesh_smooth_step: verts_out must not be verts_in (every vertex reads its neighbours' old positions)");
     hipLaunchKernelGGL(me_smooth_kernel, dim3(blocks(V)), dim3(ME_THREADS), 0, (hipStream_t)stream, V, A, verts_in, adj_offset, adj, adj_kind,
                        vert_flag, factor, boundary, verts_out);
-    return edone();
+    return launch_status();
 }
 
 }  // extern "C"

@@ -25,13 +25,9 @@
 #include <float.h>
 #include <math.h>
 
-#include "dgm_common.hpp"
+#include "dgm_host.hpp"
 
 #pragma clang fp contract(off)
-
-namespace dgm {
-void set_last_error(const char* msg);
-}  // namespace dgm
 
 namespace {
 using namespace dgm;
@@ -44,14 +40,6 @@ constexpr double WN_FOUR_PI = 12.566370614359172;  // 4 * M_PI
 
 static_assert(WN_CHUNK == WN_THREADS, "one face per thread when staging");
 
-int pfail(const char* m) {
-    set_last_error(m);
-    return 1;
-}
-int pdone() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : pfail(hipGetErrorString(e));
-}
 
 long long slices_of(int F) { return ((long long)F + WN_SLICE - 1) / WN_SLICE; }
 
@@ -168,27 +156,27 @@ size_t dgm_wind_scratch_bytes(int N, int F) {
 }
 
 int dgm_wind_number(int N, int V, int F, const float* points, const float* verts, const int* faces, char* scratch, float* w, void* stream) {
-    if (N < 0 || V < 0 || F < 0) return pfail("wind_number: need N >= 0, V >= 0 and F >= 0");
-    if (F > 0x7fffffff - WN_CHUNK) return pfail("wind_number: too many faces");
+    if (N < 0 || V < 0 || F < 0) return fail("wind_number: need N >= 0, V >= 0 and F >= 0");
+    if (F > 0x7fffffff - WN_CHUNK) return fail("wind_number: too many faces");
     if (N == 0) return 0;  // (before any HIP call)
-    if (!points || !w || (F > 0 && !faces) || (F > 0 && V > 0 && !verts)) return pfail("wind_number: NULL pointer");
+    if (!points || !w || (F > 0 && !faces) || (F > 0 && V > 0 && !verts)) return fail("wind_number: NULL pointer");
     const long long S = slices_of(F), nqb = ((long long)N + WN_THREADS - 1) / WN_THREADS;
-    if (S > 1 && !scratch) return pfail("wind_number: NULL scratch");
-    if (S > 1 && ((uintptr_t)scratch & 7)) return pfail("wind_number: scratch must be 8-byte aligned");
-    if (nqb * (S > 0 ? S : 1) > 0x7fffffffLL) return pfail("wind_number: N x slices over the supported grid, split N");
+    if (S > 1 && !scratch) return fail("wind_number: NULL scratch");
+    if (S > 1 && ((uintptr_t)scratch & 7)) return fail("wind_number: scratch must be 8-byte aligned");
+    if (nqb * (S > 0 ? S : 1) > 0x7fffffffLL) return fail("wind_number: N x slices over the supported grid, split N");
     hipStream_t st = (hipStream_t)stream;
     if (F == 0 || V == 0) {
         hipLaunchKernelGGL(wind_none_kernel, dim3((unsigned)nqb), dim3(WN_THREADS), 0, st, N, points, w);
-        return pdone();
+        return launch_status();
     }
     if (S == 1) {
         hipLaunchKernelGGL(wind_kernel<true>, dim3((unsigned)nqb), dim3(WN_THREADS), 0, st, N, V, F, 1, points, verts, faces, (double*)nullptr, w);
-        return pdone();
+        return launch_status();
     }
     double* sums = (double*)scratch;
     hipLaunchKernelGGL(wind_kernel<false>, dim3((unsigned)(nqb * S)), dim3(WN_THREADS), 0, st, N, V, F, (int)S, points, verts, faces, sums, w);
     hipLaunchKernelGGL(wind_total_kernel, dim3((unsigned)nqb), dim3(WN_THREADS), 0, st, N, (int)S, (const double*)sums, w);
-    return pdone();
+    return launch_status();
 }
 
 }  // extern "C"

@@ -21,11 +21,7 @@
 // segment between the centres at distance t from the front centre: t > .5 blends (t - .5) of the front colour into the other
 // pixel, t < .5 blends (.5 - t) of the other colour into the front pixel.  Edge topology: an open-addressing hash of the
 // undirected edges built per call (face count and xor of the third vertices), reused by the backward.
-#include "dgm_common.hpp"
-
-namespace dgm {
-void set_last_error(const char* msg);  // c_api.hip
-}
+#include "dgm_host.hpp"
 
 using namespace dgm;
 
@@ -532,20 +528,11 @@ aa_backward_kernel(AaCtx c, int C, const float* __restrict__ color, const float*
     }
 }
 
-int tfail(const char* m) {
-    dgm::set_last_error(m);
-    return 1;
-}
-int tdone() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : tfail(hipGetErrorString(e));
-}
 
 bool tr_dims(int V, int F, int H, int W) {
     return V >= 0 && F >= 0 && F < (1 << 24) && H > 0 && W > 0 && H <= TR_MAX_DIM && W <= TR_MAX_DIM;
 }
 
-unsigned blocks(long long n) { return (unsigned)((n + TR_THREADS - 1) / TR_THREADS); }
 
 }  // namespace
 
@@ -556,15 +543,15 @@ size_t dgm_tri_raster_scratch_bytes(int F, int H, int W) {
 }
 
 int dgm_tri_rasterize_forward(int V, int F, int H, int W, const float* pos, const int* tri, char* scratch, float* rast, void* stream) {
-    if (!tr_dims(V, F, H, W)) return tfail("tri_rasterize: need V >= 0, 0 <= F < 2^24 and 0 < H, W <= 16384");
-    if (!scratch || !rast || (F > 0 && (!tri || (V > 0 && !pos)))) return tfail("tri_rasterize: NULL pointer");
+    if (!tr_dims(V, F, H, W)) return fail("tri_rasterize: need V >= 0, 0 <= F < 2^24 and 0 < H, W <= 16384");
+    if (!scratch || !rast || (F > 0 && (!tri || (V > 0 && !pos)))) return fail("tri_rasterize: NULL pointer");
     const RastLayout L = rast_layout(F, H, W);
     hipStream_t st = (hipStream_t)stream;
     unsigned long long* keys = (unsigned long long*)(scratch + L.keys);
     unsigned* counter = (unsigned*)(scratch + L.counter);
     if (hipMemsetAsync(keys, 0xff, (size_t)H * W * sizeof(unsigned long long), st) != hipSuccess ||
         hipMemsetAsync(counter, 0, sizeof(unsigned), st) != hipSuccess)
-        return tfail("tri_rasterize: memset failed");
+        return fail("tri_rasterize: memset failed");
     if (F > 0 && V > 0) {
         hipLaunchKernelGGL(raster_small_kernel, dim3(blocks(F)), dim3(TR_THREADS), 0, st, V, F, H, W, (const float4*)pos, tri, keys,
                            (int*)(scratch + L.list), counter);
@@ -573,41 +560,41 @@ int dgm_tri_rasterize_forward(int V, int F, int H, int W, const float* pos, cons
     }
     hipLaunchKernelGGL(raster_resolve_kernel, dim3(blocks((long long)H * W)), dim3(TR_THREADS), 0, st, V, H, W, (const float4*)pos, tri,
                        (const unsigned long long*)keys, (float4*)rast);
-    return tdone();
+    return launch_status();
 }
 
 int dgm_tri_rasterize_backward(int V, int F, int H, int W, const float* pos, const int* tri, const float* rast, const float* drast,
                                float* dpos, void* stream) {
-    if (!tr_dims(V, F, H, W)) return tfail("tri_rasterize_backward: need V >= 0, 0 <= F < 2^24 and 0 < H, W <= 16384");
-    if (!rast || !drast || (V > 0 && (!pos || !dpos)) || (F > 0 && !tri)) return tfail("tri_rasterize_backward: NULL pointer");
+    if (!tr_dims(V, F, H, W)) return fail("tri_rasterize_backward: need V >= 0, 0 <= F < 2^24 and 0 < H, W <= 16384");
+    if (!rast || !drast || (V > 0 && (!pos || !dpos)) || (F > 0 && !tri)) return fail("tri_rasterize_backward: NULL pointer");
     hipStream_t st = (hipStream_t)stream;
-    if (V == 0) return tdone();
-    if (hipMemsetAsync(dpos, 0, (size_t)V * 4 * sizeof(float), st) != hipSuccess) return tfail("tri_rasterize_backward: memset failed");
+    if (V == 0) return launch_status();
+    if (hipMemsetAsync(dpos, 0, (size_t)V * 4 * sizeof(float), st) != hipSuccess) return fail("tri_rasterize_backward: memset failed");
     if (F > 0)
         hipLaunchKernelGGL(raster_backward_kernel, dim3(blocks((long long)H * W)), dim3(TR_THREADS), 0, st, V, F, H, W, (const float4*)pos,
                            tri, (const float4*)rast, (const float4*)drast, dpos);
-    return tdone();
+    return launch_status();
 }
 
 int dgm_tri_interpolate_forward(int V, int F, int H, int W, int C, const float* attr, const float* rast, const int* tri, float* out,
                                 void* stream) {
-    if (!tr_dims(V, F, H, W) || C <= 0) return tfail("tri_interpolate: need V >= 0, 0 <= F < 2^24, 0 < H, W <= 16384 and C > 0");
-    if (!rast || !out || (V > 0 && !attr) || (F > 0 && !tri)) return tfail("tri_interpolate: NULL pointer");
+    if (!tr_dims(V, F, H, W) || C <= 0) return fail("tri_interpolate: need V >= 0, 0 <= F < 2^24, 0 < H, W <= 16384 and C > 0");
+    if (!rast || !out || (V > 0 && !attr) || (F > 0 && !tri)) return fail("tri_interpolate: NULL pointer");
     hipLaunchKernelGGL(interp_forward_kernel, dim3(blocks((long long)H * W)), dim3(TR_THREADS), 0, (hipStream_t)stream, V, F, H * W, C,
                        attr, (const float4*)rast, tri, out);
-    return tdone();
+    return launch_status();
 }
 
 int dgm_tri_interpolate_backward(int V, int F, int H, int W, int C, const float* attr, const float* rast, const int* tri,
                                  const float* dout, float* dattr, float* drast, void* stream) {
-    if (!tr_dims(V, F, H, W) || C <= 0) return tfail("tri_interpolate_backward: need V >= 0, 0 <= F < 2^24, 0 < H, W <= 16384 and C > 0");
-    if (!rast || !dout || !drast || (V > 0 && (!attr || !dattr)) || (F > 0 && !tri)) return tfail("tri_interpolate_backward: NULL pointer");
+    if (!tr_dims(V, F, H, W) || C <= 0) return fail("tri_interpolate_backward: need V >= 0, 0 <= F < 2^24, 0 < H, W <= 16384 and C > 0");
+    if (!rast || !dout || !drast || (V > 0 && (!attr || !dattr)) || (F > 0 && !tri)) return fail("tri_interpolate_backward: NULL pointer");
     hipStream_t st = (hipStream_t)stream;
     if (V > 0 && hipMemsetAsync(dattr, 0, (size_t)V * C * sizeof(float), st) != hipSuccess)
-        return tfail("tri_interpolate_backward: memset failed");
+        return fail("tri_interpolate_backward: memset failed");
     hipLaunchKernelGGL(interp_backward_kernel, dim3(blocks((long long)H * W)), dim3(TR_THREADS), 0, st, V, F, H * W, C, attr,
                        (const float4*)rast, tri, dout, dattr, (float4*)drast);
-    return tdone();
+    return launch_status();
 }
 
 size_t dgm_tri_aa_scratch_bytes(int F) {
@@ -616,34 +603,34 @@ size_t dgm_tri_aa_scratch_bytes(int F) {
 
 int dgm_tri_antialias_forward(int V, int F, int H, int W, int C, const float* color, const float* rast, const float* pos, const int* tri,
                               char* scratch, float* out, void* stream) {
-    if (!tr_dims(V, F, H, W) || C <= 0) return tfail("tri_antialias: need V >= 0, 0 <= F < 2^24, 0 < H, W <= 16384 and C > 0");
-    if (!color || !rast || !scratch || !out || (V > 0 && !pos) || (F > 0 && !tri)) return tfail("tri_antialias: NULL pointer");
+    if (!tr_dims(V, F, H, W) || C <= 0) return fail("tri_antialias: need V >= 0, 0 <= F < 2^24, 0 < H, W <= 16384 and C > 0");
+    if (!color || !rast || !scratch || !out || (V > 0 && !pos) || (F > 0 && !tri)) return fail("tri_antialias: NULL pointer");
     const AaLayout L = aa_layout(F);
     hipStream_t st = (hipStream_t)stream;
     unsigned long long* keys = (unsigned long long*)(scratch + L.keys);
     uint2* vals = (uint2*)(scratch + L.vals);
     if (hipMemsetAsync(keys, 0xff, (size_t)L.cap * sizeof(unsigned long long), st) != hipSuccess ||
         hipMemsetAsync(vals, 0, (size_t)L.cap * sizeof(uint2), st) != hipSuccess)
-        return tfail("tri_antialias: memset failed");
+        return fail("tri_antialias: memset failed");
     if (F > 0) hipLaunchKernelGGL(topo_build_kernel, dim3(blocks(F)), dim3(TR_THREADS), 0, st, V, F, tri, L.cap, keys, vals);
     const AaCtx c{V, F, H, W, (const float4*)pos, tri, (const float4*)rast, L.cap, keys, vals};
     hipLaunchKernelGGL(aa_forward_kernel, dim3(blocks((long long)H * W)), dim3(TR_THREADS), 0, st, c, C, color, out);
-    return tdone();
+    return launch_status();
 }
 
 int dgm_tri_antialias_backward(int V, int F, int H, int W, int C, const float* color, const float* rast, const float* pos, const int* tri,
                                const char* scratch, const float* dout, float* dcolor, float* dpos, void* stream) {
-    if (!tr_dims(V, F, H, W) || C <= 0) return tfail("tri_antialias_backward: need V >= 0, 0 <= F < 2^24, 0 < H, W <= 16384 and C > 0");
+    if (!tr_dims(V, F, H, W) || C <= 0) return fail("tri_antialias_backward: need V >= 0, 0 <= F < 2^24, 0 < H, W <= 16384 and C > 0");
     if (!color || !rast || !scratch || !dout || !dcolor || (V > 0 && (!pos || !dpos)) || (F > 0 && !tri))
-        return tfail("tri_antialias_backward: NULL pointer");
+        return fail("tri_antialias_backward: NULL pointer");
     const AaLayout L = aa_layout(F);
     hipStream_t st = (hipStream_t)stream;
     if (V > 0 && hipMemsetAsync(dpos, 0, (size_t)V * 4 * sizeof(float), st) != hipSuccess)
-        return tfail("tri_antialias_backward: memset failed");
+        return fail("tri_antialias_backward: memset failed");
     const AaCtx c{V, F, H, W, (const float4*)pos, tri, (const float4*)rast, L.cap, (const unsigned long long*)(scratch + L.keys),
                   (const uint2*)(scratch + L.vals)};
     hipLaunchKernelGGL(aa_backward_kernel, dim3(blocks((long long)H * W)), dim3(TR_THREADS), 0, st, c, C, color, dout, dcolor, dpos);
-    return tdone();
+    return launch_status();
 }
 
 }  // extern "C"

@@ -63,16 +63,10 @@
 #include <math.h>
 #include <stdio.h>
 
-#include "dgm_common.hpp"
+#include "dgm_host.hpp"
+#include "mesh_grid.hpp"
 
 #pragma clang fp contract(off)
-
-namespace dgm {
-size_t radix_sort_hist_words(int n);
-const unsigned* radix_sort_pairs(hipStream_t st, int n, int passes, unsigned* keysA, unsigned* valsA, unsigned* keysB,
-                                 unsigned* valsB, unsigned* hist, unsigned* scanned);
-void set_last_error(const char* msg);
-}  // namespace dgm
 
 namespace {
 using namespace dgm;
@@ -83,19 +77,9 @@ constexpr int RC_BOX_PARTS = 128;  // partial boxes of the centroids
 constexpr float RC_PAD = 9.5367431640625e-07f;  // 2^-20 (file header, Z)
 constexpr int RC_MAX_F = 0x7fffffff - RC_CHUNK;
 
-static_assert(RC_CHUNK == RC_THREADS, "one face per thread when staging");
-
-int rfail(const char* m) {
-    set_last_error(m);
-    return 1;
-}
-int rdone() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : rfail(hipGetErrorString(e));
-}
+static_assert(RC_CHUNK == RC_THREADS && RC_THREADS == BOX_THREADS, "one face per thread when staging and in the box reduction");
 
 long long chunks_of(int F) { return ((long long)F + RC_CHUNK - 1) / RC_CHUNK; }
-unsigned blocks(long long n) { return (unsigned)((n + RC_THREADS - 1) / RC_THREADS); }
 
 __device__ __forceinline__ bool finite1(float x) { return fabsf(x) < INFINITY; }
 __device__ __forceinline__ bool finite3(float x, float y, float z) { return finite1(x) && finite1(y) && finite1(z); }
@@ -349,58 +333,25 @@ centroid_kernel(int V, int F, const float* __restrict__ verts, const int* __rest
                 : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-__device__ __forceinline__ void reduce_box(float red[6][RC_THREADS], const float p[3], const float q[3]) {
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        red[a][threadIdx.x] = p[a];
-        red[3 + a][threadIdx.x] = q[a];
-    }
-    __syncthreads();
-    for (int off = RC_THREADS / 2; off >= 1; off >>= 1) {  // ends after log2(256) rounds
-        if ((int)threadIdx.x < off) {
-#pragma unroll
-            for (int a = 0; a < 3; a++) {
-                red[a][threadIdx.x] = fminf(red[a][threadIdx.x], red[a][threadIdx.x + off]);
-                red[3 + a][threadIdx.x] = fmaxf(red[3 + a][threadIdx.x], red[3 + a][threadIdx.x + off]);
-            }
-        }
-        __syncthreads();
-    }
-}
-
 // partial[b] = the box of the valid centroids block b visits (min and max are exact: the order does not matter)
 __global__ void __launch_bounds__(RC_THREADS) centroid_box_kernel(int F, const float4* __restrict__ cen, float* __restrict__ partial) {
-    __shared__ float red[6][RC_THREADS];
-    float p[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, q[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+    float v[6];
+    box_start<6>(v);
     for (long long f = (long long)blockIdx.x * RC_THREADS + threadIdx.x; f < F; f += (long long)gridDim.x * RC_THREADS) {  // ends at F
         const float4 c = cen[f];
         if (c.w == 0.f) continue;
-        p[0] = fminf(p[0], c.x);
-        p[1] = fminf(p[1], c.y);
-        p[2] = fminf(p[2], c.z);
-        q[0] = fmaxf(q[0], c.x);
-        q[1] = fmaxf(q[1], c.y);
-        q[2] = fmaxf(q[2], c.z);
+        const float p[3] = {c.x, c.y, c.z};
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            v[a] = box_join(a, v[a], p[a]);
+            v[3 + a] = box_join(3 + a, v[3 + a], p[a]);
+        }
     }
-    reduce_box(red, p, q);
-    if (threadIdx.x < 6) partial[blockIdx.x * 6 + threadIdx.x] = red[threadIdx.x][0];
+    box_reduce_partial<6>(v, partial);
 }
 
 __global__ void centroid_box_final_kernel(int nparts, const float* __restrict__ partial, float* __restrict__ bbox) {
-    if (threadIdx.x < 6) {
-        float v = threadIdx.x < 3 ? FLT_MAX : -FLT_MAX;
-        for (int b = 0; b < nparts; b++)  // ends at the last partial box: at most RC_BOX_PARTS rounds
-            v = threadIdx.x < 3 ? fminf(v, partial[b * 6 + threadIdx.x]) : fmaxf(v, partial[b * 6 + threadIdx.x]);
-        bbox[threadIdx.x] = v;
-    }
-}
-
-__device__ __forceinline__ unsigned spread10(unsigned x) {  // ten bits, two zeros between neighbours (knn.hip)
-    x = (x | (x << 16)) & 0x030000FF;
-    x = (x | (x << 8)) & 0x0300F00F;
-    x = (x | (x << 4)) & 0x030C30C3;
-    x = (x | (x << 2)) & 0x09249249;
-    return x;
+    if (threadIdx.x < 6) bbox[threadIdx.x] = box_final_row<6>(nparts, partial, threadIdx.x);  // (at most RC_BOX_PARTS rounds)
 }
 
 // key = the 30-bit Morton code of the centroid in the centroids' box, 0xFFFFFFFF for a face that can never hit; value = the face.
@@ -415,7 +366,7 @@ morton_kernel(int F, const float4* __restrict__ cen, const float* __restrict__ b
 #pragma unroll
     for (int a = 0; a < 3; a++) {
         const float lo = bbox[a], hi = bbox[3 + a];
-        q[a] = spread10(min(f2u_sat(((p[a] - lo) / (hi - lo)) * 1023.f), 1023u));  // (a flat box: 0 / 0 = NaN -> 0)
+        q[a] = morton_spread10(min(f2u_sat(((p[a] - lo) / (hi - lo)) * 1023.f), 1023u));  // (a flat box: 0 / 0 = NaN -> 0)
     }
     keys[f] = c.w == 0.f ? 0xFFFFFFFFu : (q[0] | (q[1] << 1) | (q[2] << 2));
     vals[f] = (unsigned)f;
@@ -434,17 +385,18 @@ chunk_kernel(int V, int F, const float* __restrict__ verts, const int* __restric
     tri[3 * at] = make_float4(c[0], c[1], c[2], c[3]);
     tri[3 * at + 1] = make_float4(c[4], c[5], c[6], c[7]);
     tri[3 * at + 2] = make_float4(c[8], __int_as_float(f), 0.f, 0.f);
-    float p[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, q[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+    float v[6];
+    box_start<6>(v);
     if (ok) {
 #pragma unroll
         for (int a = 0; a < 3; a++) {
-            p[a] = fminf(fminf(c[a], c[3 + a]), c[6 + a]);
-            q[a] = fmaxf(fmaxf(c[a], c[3 + a]), c[6 + a]);
+            v[a] = fminf(fminf(c[a], c[3 + a]), c[6 + a]);
+            v[3 + a] = fmaxf(fmaxf(c[a], c[3 + a]), c[6 + a]);
         }
     }
     const unsigned long long valid = __ballot(ok);
     if (lane_id() == 0) count[threadIdx.x >> 6] = (unsigned)__popcll(valid);
-    reduce_box(red, p, q);  // (its barriers also publish count)
+    box_reduce<6>(red, v);  // (its barriers also publish count)
     if (threadIdx.x == 0) {
         const unsigned n = count[0] + count[1] + count[2] + count[3];
         boxes[2 * blockIdx.x] = make_float4(red[0][0], red[1][0], red[2][0], (float)n);
@@ -509,7 +461,7 @@ int launch_cast(int N, int V, int F, const float* origins, const float* dirs, fl
         const float4* boxes = tri + nch * RC_CHUNK * 3;
         hipLaunchKernelGGL(ray_accel_kernel<ANY>, grid, block, 0, st, N, (int)nch, origins, dirs, t_min, t_max, tri, boxes, face, t, bary, hit);
     }
-    return rdone();
+    return launch_status();
 }
 
 }  // namespace
@@ -527,11 +479,11 @@ size_t dgm_ray_build_scratch_bytes(int F) {
 }
 
 int dgm_ray_build(int V, int F, const float* verts, const int* faces, char* scratch, char* accel, void* stream) {
-    if (V < 0 || F < 0) return rfail("ray_build: need V >= 0 and F >= 0");
-    if (F > RC_MAX_F) return rfail("ray_build: too many faces");
+    if (V < 0 || F < 0) return fail("ray_build: need V >= 0 and F >= 0");
+    if (F > RC_MAX_F) return fail("ray_build: too many faces");
     if (F == 0) return 0;  // (before any HIP call: the structure of no face has no byte)
-    if (!faces || !scratch || !accel || (V > 0 && !verts)) return rfail("ray_build: NULL pointer");
-    if ((uintptr_t)accel & 15) return rfail("ray_build: accel must be 16-byte aligned");
+    if (!faces || !scratch || !accel || (V > 0 && !verts)) return fail("ray_build: NULL pointer");
+    if ((uintptr_t)accel & 15) return fail("ray_build: accel must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const BuildLayout L = build_layout(F);
     char* base = align_ptr(scratch);
@@ -550,19 +502,19 @@ int dgm_ray_build(int V, int F, const float* verts, const int* faces, char* scra
     hipLaunchKernelGGL(morton_kernel, dim3(blocks(F)), dim3(RC_THREADS), 0, st, F, (const float4*)cen, (const float*)bbox, keysA, valsA);
     const unsigned* order = radix_sort_pairs(st, F, 4, keysA, valsA, keysB, valsB, (unsigned*)(base + L.hist), (unsigned*)(base + L.scanned));
     hipLaunchKernelGGL(chunk_kernel, dim3((unsigned)nch), dim3(RC_THREADS), 0, st, V, F, verts, faces, order, tri, boxes);
-    return rdone();
+    return launch_status();
 }
 
 int dgm_ray_cast(int N, int V, int F, const float* origins, const float* dirs, float t_min, float t_max, const float* verts, const int* faces,
                  const char* accel, int* face, float* t, float* bary, void* stream) {
-    if (const char* m = cast_args("ray_cast", N, V, F, origins, dirs, verts, faces, accel, face && t && bary)) return rfail(m);
+    if (const char* m = cast_args("ray_cast", N, V, F, origins, dirs, verts, faces, accel, face && t && bary)) return fail(m);
     if (N == 0) return 0;  // (before any HIP call)
     return launch_cast<false>(N, V, F, origins, dirs, t_min, t_max, verts, faces, accel, face, t, bary, nullptr, (hipStream_t)stream);
 }
 
 int dgm_ray_occluded(int N, int V, int F, const float* origins, const float* dirs, float t_min, float t_max, const float* verts,
                      const int* faces, const char* accel, unsigned char* hit, void* stream) {
-    if (const char* m = cast_args("ray_occluded", N, V, F, origins, dirs, verts, faces, accel, hit != nullptr)) return rfail(m);
+    if (const char* m = cast_args("ray_occluded", N, V, F, origins, dirs, verts, faces, accel, hit != nullptr)) return fail(m);
     if (N == 0) return 0;  // (before any HIP call)
     return launch_cast<true>(N, V, F, origins, dirs, t_min, t_max, verts, faces, accel, nullptr, nullptr, nullptr, hit, (hipStream_t)stream);
 }

@@ -28,14 +28,10 @@
 #include <math.h>
 #include <stdio.h>
 
-#include "dgm_common.hpp"
+#include "dgm_host.hpp"
 #include "mesh_scan.hpp"
 
 #pragma clang fp contract(off)
-
-namespace dgm {
-void set_last_error(const char* msg);
-}  // namespace dgm
 
 namespace {
 using namespace dgm;
@@ -49,17 +45,8 @@ constexpr int SP_MAX_DIM = 1 << 20;
 constexpr unsigned long long KEY_EMPTY = ~0ull;
 constexpr int SLOT_EMPTY = -1;
 
-unsigned blocks(long long n, int t = SP_THREADS) { return (unsigned)((n + t - 1) / t); }
 int tiles(long long n) { return (int)((n + SP_TILE - 1) / SP_TILE); }
 
-int sfail(const char* m) {
-    set_last_error(m);
-    return 1;
-}
-int sdone() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : sfail(hipGetErrorString(e));
-}
 
 #define AGENT __HIP_MEMORY_SCOPE_AGENT
 
@@ -546,11 +533,11 @@ int check_sizes(const char* who, int V, int F) {
     static thread_local char msg[160];
     if (V < 0 || F < 0) {
         snprintf(msg, sizeof msg, "%s: need V >= 0 and F >= 0", who);
-        return sfail(msg);
+        return fail(msg);
     }
     if (F > SP_MAX_FACES) {
         snprintf(msg, sizeof msg, "%s: F = %d is over the supported %d faces", who, F, SP_MAX_FACES);
-        return sfail(msg);
+        return fail(msg);
     }
     return 0;
 }
@@ -559,20 +546,20 @@ int check_grid(const char* who, float ox, float oy, float oz, int nx, int ny, in
     static thread_local char msg[256];
     if (!(h > 0.f) || !(h <= FLT_MAX)) {
         snprintf(msg, sizeof msg, "%s: need a finite cell size h > 0, got %g", who, (double)h);
-        return sfail(msg);
+        return fail(msg);
     }
     if (nx < 1 || ny < 1 || nz < 1) {
         snprintf(msg, sizeof msg, "%s: need grid dimensions >= 1, got %d x %d x %d", who, nx, ny, nz);
-        return sfail(msg);
+        return fail(msg);
     }
     if (nx > SP_MAX_DIM || ny > SP_MAX_DIM || nz > SP_MAX_DIM) {
         snprintf(msg, sizeof msg, "%s: a grid of %d x %d x %d cells of size %g is over the limit of 2^20 cells per axis", who, nx, ny, nz,
                  (double)h);
-        return sfail(msg);
+        return fail(msg);
     }
     if (!(ox == ox) || !(oy == oy) || !(oz == oz) || fabsf(ox) > FLT_MAX || fabsf(oy) > FLT_MAX || fabsf(oz) > FLT_MAX) {
         snprintf(msg, sizeof msg, "%s: need a finite box origin", who);
-        return sfail(msg);
+        return fail(msg);
     }
     return 0;
 }
@@ -588,13 +575,13 @@ size_t dgm_mesh_simplify_scratch_bytes(int V, int F) {
 
 int dgm_mesh_simplify_box(int V, int F, const float* verts, const int* faces, char* scratch, float* box, void* stream) {
     if (check_sizes("mesh_simplify_box", V, F)) return 1;
-    if (!scratch || !box || (V > 0 && !verts) || (F > 0 && !faces)) return sfail("mesh_simplify_box: NULL pointer");
+    if (!scratch || !box || (V > 0 && !verts) || (F > 0 && !faces)) return fail("mesh_simplify_box: NULL pointer");
     hipStream_t st = (hipStream_t)stream;
     const SimplifyScratch s = simplify_layout(scratch, V, F);
-    if (V > 0 && hipMemsetAsync(s.used, 0, (size_t)V * 4, st) != hipSuccess) return sdone();
+    if (V > 0 && hipMemsetAsync(s.used, 0, (size_t)V * 4, st) != hipSuccess) return launch_status();
     if (F > 0) hipLaunchKernelGGL(sp_box_kernel, dim3(blocks(F)), dim3(SP_THREADS), 0, st, V, F, verts, faces, s.fvalid, s.used, s.partial);
     hipLaunchKernelGGL(sp_box_reduce_kernel, dim3(1), dim3(SP_THREADS), 0, st, (int)blocks(F), (const unsigned*)s.partial, s.box, box);
-    return sdone();
+    return launch_status();
 }
 
 int dgm_mesh_simplify_count(int V, int F, const float* verts, const int* faces, float ox, float oy, float oz, int nx, int ny, int nz,
@@ -603,7 +590,7 @@ int dgm_mesh_simplify_count(int V, int F, const float* verts, const int* faces, 
     if (check_sizes("mesh_simplify_count", V, F)) return 1;
     if (check_grid("mesh_simplify_count", ox, oy, oz, nx, ny, nz, h)) return 1;
     if (!scratch || !compact_scratch || !counts || (V > 0 && !verts) || (F > 0 && (!faces || !rep_faces || !keep)))
-        return sfail("mesh_simplify_count: NULL pointer");
+        return fail("mesh_simplify_count: NULL pointer");
     hipStream_t st = (hipStream_t)stream;
     const SimplifyScratch s = simplify_layout(scratch, V, F);
     const Grid g = {ox, oy, oz, h, nx, ny, nz};
@@ -623,7 +610,7 @@ int dgm_mesh_simplify_count(int V, int F, const float* verts, const int* faces, 
         hipLaunchKernelGGL(sp_dup_flag_kernel, dim3(blocks(F)), dim3(SP_THREADS), 0, st, F, (const int*)rep_faces, s.cap_f, s.owner,
                            (const int*)s.first, keep);
     }
-    if (sdone()) return 1;
+    if (launch_status()) return 1;
     return dgm_mesh_compact_count(V, F, rep_faces, keep, compact_scratch, counts, stream);
 }
 
@@ -631,16 +618,16 @@ int dgm_mesh_simplify_place(int V, int F, const float* verts, const int* faces, 
                             int ny, int nz, float h, double regularization, char* scratch, float* placed, void* stream) {
     if (check_sizes("mesh_simplify_place", V, F)) return 1;
     if (check_grid("mesh_simplify_place", ox, oy, oz, nx, ny, nz, h)) return 1;
-    if (!(regularization >= 0.0) || !(regularization <= DBL_MAX)) return sfail("mesh_simplify_place: need a finite regularization >= 0");
-    if (!scratch || (V > 0 && (!verts || !placed)) || (F > 0 && (!faces || !rep_faces))) return sfail("mesh_simplify_place: NULL pointer");
+    if (!(regularization >= 0.0) || !(regularization <= DBL_MAX)) return fail("mesh_simplify_place: need a finite regularization >= 0");
+    if (!scratch || (V > 0 && (!verts || !placed)) || (F > 0 && (!faces || !rep_faces))) return fail("mesh_simplify_place: NULL pointer");
     if (V == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const SimplifyScratch s = simplify_layout(scratch, V, F);
     const Grid g = {ox, oy, oz, h, nx, ny, nz};
     unsigned* total = s.box + 8;
-    if (hipMemsetAsync(s.count, 0, (size_t)V * 4, st) != hipSuccess) return sdone();
+    if (hipMemsetAsync(s.count, 0, (size_t)V * 4, st) != hipSuccess) return launch_status();
     if (F > 0) hipLaunchKernelGGL(sp_inst_count_kernel, dim3(blocks(F)), dim3(SP_THREADS), 0, st, V, F, rep_faces, s.count);
-    scan_exclusive(st, (long long)V, (const unsigned*)s.count, s.tile_total, s.tile_off, s.offset, s.cursor, total);
+    scan_exclusive(st, (long long)V, (const unsigned*)s.count, s.tile_total, s.tile_off, s.offset, s.cursor, false, total);
     if (F > 0) {
         hipLaunchKernelGGL(sp_inst_fill_kernel, dim3(blocks(F)), dim3(SP_THREADS), 0, st, V, F, rep_faces, (const unsigned*)s.offset, s.cursor,
                            3ull * (unsigned long long)F, s.inst_face, s.inst_rep);
@@ -650,20 +637,20 @@ int dgm_mesh_simplify_place(int V, int F, const float* verts, const int* faces, 
     hipLaunchKernelGGL(sp_place_kernel, dim3(blocks(V)), dim3(SP_THREADS), 0, st, V, F, verts, faces, (const int*)s.rep,
                        (const unsigned long long*)s.vkey, (const unsigned*)s.offset, (const unsigned*)s.count, (const int*)s.sorted, g,
                        regularization, placed);
-    return sdone();
+    return launch_status();
 }
 
 int dgm_mesh_simplify_vert_map(int V, int F, int Vn, const int* vert_index, char* scratch, int* vert_map, void* stream) {
     if (check_sizes("mesh_simplify_vert_map", V, F)) return 1;
-    if (Vn < 0 || Vn > V) return sfail("mesh_simplify_vert_map: need 0 <= Vn <= V");
-    if (!scratch || (V > 0 && !vert_map) || (Vn > 0 && !vert_index)) return sfail("mesh_simplify_vert_map: NULL pointer");
+    if (Vn < 0 || Vn > V) return fail("mesh_simplify_vert_map: need 0 <= Vn <= V");
+    if (!scratch || (V > 0 && !vert_map) || (Vn > 0 && !vert_index)) return fail("mesh_simplify_vert_map: NULL pointer");
     if (V == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const SimplifyScratch s = simplify_layout(scratch, V, F);
-    if (hipMemsetAsync(s.newidx, 0xff, (size_t)V * 4, st) != hipSuccess) return sdone();  // (-1)
+    if (hipMemsetAsync(s.newidx, 0xff, (size_t)V * 4, st) != hipSuccess) return launch_status();  // (-1)
     if (Vn > 0) hipLaunchKernelGGL(sp_newidx_kernel, dim3(blocks(Vn)), dim3(SP_THREADS), 0, st, V, Vn, vert_index, s.newidx);
     hipLaunchKernelGGL(sp_vert_map_kernel, dim3(blocks(V)), dim3(SP_THREADS), 0, st, V, (const int*)s.rep, (const int*)s.newidx, vert_map);
-    return sdone();
+    return launch_status();
 }
 
 }  // extern "C"

@@ -37,13 +37,9 @@
 // One thread per texel; every texel of out and face_id is written.  No atomics, no scratch, bit-reproducible.
 #include <math.h>
 
-#include "dgm_common.hpp"
+#include "dgm_host.hpp"
 
 #pragma clang fp contract(off)
-
-namespace dgm {
-void set_last_error(const char* msg);
-}  // namespace dgm
 
 namespace {
 using namespace dgm;
@@ -53,14 +49,6 @@ constexpr int TX_MAX_SIDE = 16384;  // texture and atlas sides: (float)side and 
 
 enum { TX_WRAP = DGM_TEX_WRAP, TX_CLAMP = DGM_TEX_CLAMP, TX_ZERO = DGM_TEX_ZERO };
 
-int xfail(const char* m) {
-    set_last_error(m);
-    return 1;
-}
-int xdone() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : xfail(hipGetErrorString(e));
-}
 
 __device__ __forceinline__ bool finitef(float x) { return fabsf(x) < INFINITY; }
 
@@ -304,9 +292,9 @@ const char* atlas_args(int F, int size, int cell) {
 extern "C" {
 
 int dgm_tri_texture_forward(int n, int Ht, int Wt, int C, int filter, int boundary, const float* tex, const float* uv, float* out, void* stream) {
-    if (const char* m = texture_args(n, Ht, Wt, C, filter, boundary)) return xfail(m);
+    if (const char* m = texture_args(n, Ht, Wt, C, filter, boundary)) return fail(m);
     if (n == 0) return 0;  // (before any HIP call)
-    if (!tex || !uv || !out) return xfail("tri_texture_forward: NULL pointer");
+    if (!tex || !uv || !out) return fail("tri_texture_forward: NULL pointer");
     const unsigned blocks = (unsigned)(((long long)n + TX_THREADS - 1) / TX_THREADS);
     const bool vec4 = C == 4 && !(((uintptr_t)tex | (uintptr_t)out) & 15);
     hipStream_t st = (hipStream_t)stream;
@@ -314,39 +302,39 @@ int dgm_tri_texture_forward(int n, int Ht, int Wt, int C, int filter, int bounda
         hipLaunchKernelGGL(texture_fwd_kernel<true>, dim3(blocks), dim3(TX_THREADS), 0, st, n, Ht, Wt, C, filter, boundary, tex, uv, out);
     else
         hipLaunchKernelGGL(texture_fwd_kernel<false>, dim3(blocks), dim3(TX_THREADS), 0, st, n, Ht, Wt, C, filter, boundary, tex, uv, out);
-    return xdone();
+    return launch_status();
 }
 
 int dgm_tri_texture_backward(int n, int Ht, int Wt, int C, int filter, int boundary, const float* tex, const float* uv, const float* dout,
                              float* dtex, float* duv, void* stream) {
-    if (const char* m = texture_args(n, Ht, Wt, C, filter, boundary)) return xfail(m);
-    if (!dtex) return xfail("tri_texture_backward: NULL pointer");
+    if (const char* m = texture_args(n, Ht, Wt, C, filter, boundary)) return fail(m);
+    if (!dtex) return fail("tri_texture_backward: NULL pointer");
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(dtex, 0, (size_t)Ht * Wt * C * sizeof(float), st) != hipSuccess) return xfail("tri_texture_backward: memset failed");
+    if (hipMemsetAsync(dtex, 0, (size_t)Ht * Wt * C * sizeof(float), st) != hipSuccess) return fail("tri_texture_backward: memset failed");
     if (n == 0) return 0;
-    if (!tex || !uv || !dout || !duv) return xfail("tri_texture_backward: NULL pointer");
+    if (!tex || !uv || !dout || !duv) return fail("tri_texture_backward: NULL pointer");
     const unsigned blocks = (unsigned)(((long long)n + TX_THREADS - 1) / TX_THREADS);
     hipLaunchKernelGGL(texture_bwd_kernel, dim3(blocks), dim3(TX_THREADS), 0, st, n, Ht, Wt, C, filter, boundary, tex, uv, dout, dtex, duv);
-    return xdone();
+    return launch_status();
 }
 
 int dgm_atlas_uv(int F, int size, int cell, float* uv_out, void* stream) {
-    if (const char* m = atlas_args(F, size, cell)) return xfail(m);
+    if (const char* m = atlas_args(F, size, cell)) return fail(m);
     if (F == 0) return 0;  // (before any HIP call)
-    if (!uv_out) return xfail("atlas_uv: NULL pointer");
+    if (!uv_out) return fail("atlas_uv: NULL pointer");
     const unsigned blocks = (unsigned)((3LL * F + TX_THREADS - 1) / TX_THREADS);
     hipLaunchKernelGGL(atlas_uv_kernel, dim3(blocks), dim3(TX_THREADS), 0, (hipStream_t)stream, F, size, cell, size / cell, uv_out);
-    return xdone();
+    return launch_status();
 }
 
 int dgm_atlas_interpolate(int V, int F, int C, int size, int cell, const float* attr, const int* faces, float* out, int* face_id, void* stream) {
-    if (const char* m = atlas_args(F, size, cell)) return xfail(m);
-    if (V < 0 || C < 1) return xfail("atlas_interpolate: need V >= 0 and C >= 1");
-    if (!out || !face_id || (F > 0 && !faces) || (F > 0 && V > 0 && !attr)) return xfail("atlas_interpolate: NULL pointer");
+    if (const char* m = atlas_args(F, size, cell)) return fail(m);
+    if (V < 0 || C < 1) return fail("atlas_interpolate: need V >= 0 and C >= 1");
+    if (!out || !face_id || (F > 0 && !faces) || (F > 0 && V > 0 && !attr)) return fail("atlas_interpolate: NULL pointer");
     const unsigned blocks = (unsigned)(((long long)size * size + TX_THREADS - 1) / TX_THREADS);
     hipLaunchKernelGGL(atlas_interp_kernel, dim3(blocks), dim3(TX_THREADS), 0, (hipStream_t)stream, V, F, C, size, cell, size / cell, attr, faces,
                        out, face_id);
-    return xdone();
+    return launch_status();
 }
 
 }  // extern "C"

@@ -256,7 +256,6 @@ static bool metrics_plan(int B, int C, int H, int W, int levels, MetricsPlan* P)
     return true;
 }
 
-void set_last_error(const char* msg);
 
 }  // namespace dgm
 

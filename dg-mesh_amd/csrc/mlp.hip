@@ -25,7 +25,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "dgm_common.hpp"
+#include "dgm_host.hpp"
 #include "mlp_planes.hpp"
 #include "mlp_planes5.hpp"
 
@@ -706,15 +706,10 @@ mlp_timenet_bwd_kernel(const float* __restrict__ d_out, int n_freq, const float*
 using namespace dgm;
 
 namespace dgm {
-void set_last_error(const char* msg);  // c_api.hip
 void prof_begin(int stage, hipStream_t st, int passes = 1);
 void prof_end(int stage, hipStream_t st);
 }
 namespace {
-int mlp_fail(const char* msg) {
-    dgm::set_last_error(msg);
-    return 1;
-}
 struct Ws {
     float *emb, *Y[8], *Wt[8], *Wd[8], *Ga, *Gb, *partial, *partial_db, *partial_h, *partial_hb;
     float *partial_l[8], *partial_db_l[8];  // per layer: the weight-gradient partial tiles wait for the pass's one reduction
@@ -868,14 +863,14 @@ int layer_kp(const dgm_mlp_params* p, int l) {
     return MLP_W;
 }
 int check_params(const dgm_mlp_params* p) {
-    if (!p) return mlp_fail("mlp: params is NULL");
-    if (p->n_layers != 8 || p->width != MLP_W) return mlp_fail("mlp: only D=8, W=256 is supported (the reference's only configuration)");
-    if (p->emb_dim != MLP_XE + p->t_dim || p->emb_dim > MLP_EMB) return mlp_fail("mlp: emb_dim must be 63 + t_dim <= 96");
-    if (p->skip_layer != 5) return mlp_fail("mlp: skip re-injection must feed layer 5 (skips=[4])");
-    if (p->n_out < 1 || p->n_out > 16) return mlp_fail("mlp: 1..16 head outputs supported");
+    if (!p) return fail("mlp: params is NULL");
+    if (p->n_layers != 8 || p->width != MLP_W) return fail("mlp: only D=8, W=256 is supported (the reference's only configuration)");
+    if (p->emb_dim != MLP_XE + p->t_dim || p->emb_dim > MLP_EMB) return fail("mlp: emb_dim must be 63 + t_dim <= 96");
+    if (p->skip_layer != 5) return fail("mlp: skip re-injection must feed layer 5 (skips=[4])");
+    if (p->n_out < 1 || p->n_out > 16) return fail("mlp: 1..16 head outputs supported");
     for (int l = 0; l < 8; l++)
-        if (!p->W[l] || !p->b[l]) return mlp_fail("mlp: NULL weight pointer");
-    if (!p->Wh || !p->bh) return mlp_fail("mlp: NULL head pointer");
+        if (!p->W[l] || !p->b[l]) return fail("mlp: NULL weight pointer");
+    if (!p->Wh || !p->bh) return fail("mlp: NULL head pointer");
     return 0;
 }
 
@@ -891,14 +886,14 @@ hipError_t p4_lds_attr(K kernel, int bytes, bool* done) {  // dynamic LDS above 
     {                                                                                                                  \
         static bool done_[DGM_MAX_DEVICES] = {false};                                                                  \
         if (p4_lds_attr(kernel_, cfg_lds_, &done_[current_device_slot()]) != hipSuccess)                               \
-            return mlp_fail("mlp: cannot raise the LDS limit of a plane-path kernel");                                 \
+            return fail("mlp: cannot raise the LDS limit of a plane-path kernel");                                 \
         hipLaunchKernelGGL(kernel_, dim3(grid_), dim3(512), cfg_lds_, st_, args_);                                     \
     }
 #define P5_LAUNCH(kernel_, cfg_lds_, grid_, st_, args_)                                                                \
     {                                                                                                                  \
         static bool done_[DGM_MAX_DEVICES] = {false};                                                                  \
         if (p4_lds_attr(kernel_, cfg_lds_, &done_[current_device_slot()]) != hipSuccess)                               \
-            return mlp_fail("mlp: cannot raise the LDS limit of a plane-path kernel");                                 \
+            return fail("mlp: cannot raise the LDS limit of a plane-path kernel");                                 \
         hipLaunchKernelGGL(kernel_, dim3(grid_), dim3(256), cfg_lds_, st_, args_);                                     \
     }
 typedef Gemm4Cfg<16, 1024, 512, 0, false, 8> CfgFwd;
@@ -1087,7 +1082,7 @@ int forward_planes(const dgm_mlp_params* p, int N, const float* x, const float* 
     else if (fold) P4_LAUNCH((mlp_gemm4_kernel<16, 1024, 512, 3, false, 1, true>), CfgHeadsC::LDS, gx, st, a)
     else P4_LAUNCH((mlp_gemm4_kernel<16, 1024, 512, 3, false, 1>), CfgHeads::LDS, gx, st, a)
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return mlp_fail(hipGetErrorString(e));
+    if (e != hipSuccess) return fail(hipGetErrorString(e));
     return 0;
 }
 
@@ -1141,7 +1136,7 @@ int backward_planes(const dgm_mlp_params* p, int N, const float* dOut, int temb_
     int n_dw = p4_pair_split(nt, gx);
     if (n_dw > pl.chunks) n_dw = pl.chunks;  // (the skip layer's partial buffer is carved for pl.chunks tiles of 352 rows)
     const bool per_row_t = temb_stride != 0 && dtemb != nullptr;
-    if (per_row_t && dX) return mlp_fail("mlp_backward: position gradients need a broadcast time row");
+    if (per_row_t && dX) return fail("mlp_backward: position gradients need a broadcast time row");
     for (int l = 7; l >= 0; l--) {
         const int Kp = l == 0 ? EW : (l == sk ? EW + MLP_W : MLP_W);
         const bool paired = n_dw > 0 && l >= 1;
@@ -1187,7 +1182,7 @@ int backward_planes(const dgm_mlp_params* p, int N, const float* dOut, int temb_
                 constexpr int LDS_PAIR = CfgBwdC::LDS > CfgDw::LDS ? CfgBwdC::LDS : CfgDw::LDS;
                 if ((fold ? p4_lds_attr(mlp_bwd_pair_kernel<true>, LDS_PAIR, &donec_[current_device_slot()])
                           : p4_lds_attr(mlp_bwd_pair_kernel<false>, LDS_PAIR, &done_[current_device_slot()])) != hipSuccess)
-                    return mlp_fail("mlp: cannot raise the LDS limit of mlp_bwd_pair_kernel");
+                    return fail("mlp: cannot raise the LDS limit of mlp_bwd_pair_kernel");
                 const int grid = n_dw + (gx - n_dw > 0 ? gx - n_dw : 1);
                 // chunked: the GEMM role walks the weight-gradient role's row chunks (needs as many GEMM workgroups as chunks)
                 static const int chunk_env = [] { const char* e = getenv("DGM_MLP_PAIR_CHUNKED"); return e ? atoi(e) : 1; }();
@@ -1253,7 +1248,7 @@ int backward_planes(const dgm_mlp_params* p, int N, const float* dOut, int temb_
         hipLaunchKernelGGL(mlp_dtemb_bcast_kernel, dim3(p->t_dim), dim3(256), 0, st, p->t_dim, db[0], p->W[0], layer_in(p, 0),
                            db[sk], p->W[sk], layer_in(p, sk), dtemb);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return mlp_fail(hipGetErrorString(e));
+    if (e != hipSuccess) return fail(hipGetErrorString(e));
     return 0;
 }
 
@@ -1321,7 +1316,7 @@ int backward_planes_group(const GroupNet* nets, int N, const int n_wg, hipStream
         const int g7 = nt < num_cus() ? nt : num_cus();
         static bool done_[DGM_MAX_DEVICES] = {false};
         if (p4_lds_attr(mlp_gemm4_group_kernel<1, 128, 64, 1, false, 8, true>, CfgG7C::LDS, &done_[current_device_slot()]) != hipSuccess)
-            return mlp_fail("mlp: cannot raise the LDS limit of a plane-path kernel");
+            return fail("mlp: cannot raise the LDS limit of a plane-path kernel");
         hipLaunchKernelGGL((mlp_gemm4_group_kernel<1, 128, 64, 1, false, 8, true>), dim3(g7, 2), dim3(512), CfgG7C::LDS, st, g7a);
     }
     Dw4GroupArgs dg;
@@ -1336,7 +1331,7 @@ int backward_planes_group(const GroupNet* nets, int N, const int n_wg, hipStream
         }
         static bool done_[DGM_MAX_DEVICES] = {false};
         if (p4_lds_attr(mlp_dw4_group_kernel<8, 1, 1024, 512, 128, 64>, CfgDwH::LDS, &done_[current_device_slot()]) != hipSuccess)
-            return mlp_fail("mlp: cannot raise the LDS limit of a plane-path kernel");
+            return fail("mlp: cannot raise the LDS limit of a plane-path kernel");
         hipLaunchKernelGGL((mlp_dw4_group_kernel<8, 1, 1024, 512, 128, 64>), dim3(chunks_s, 2), dim3(512), CfgDwH::LDS, st, dg);
     }
     ReduceDwBatch rb;
@@ -1364,7 +1359,7 @@ int backward_planes_group(const GroupNet* nets, int N, const int n_wg, hipStream
             }
             static bool done_[DGM_MAX_DEVICES] = {false};
             if (p4_lds_attr(mlp_dw4_group_kernel<2, 8, 256, 128, 1024, 512>, CfgDwE64::LDS, &done_[current_device_slot()]) != hipSuccess)
-                return mlp_fail("mlp: cannot raise the LDS limit of a plane-path kernel");
+                return fail("mlp: cannot raise the LDS limit of a plane-path kernel");
             hipLaunchKernelGGL((mlp_dw4_group_kernel<2, 8, 256, 128, 1024, 512>), dim3(chunks_s, 2), dim3(512), CfgDwE64::LDS, st, dg);
         }
         if (l == 0) break;
@@ -1387,7 +1382,7 @@ int backward_planes_group(const GroupNet* nets, int N, const int n_wg, hipStream
             static bool done_[DGM_MAX_DEVICES] = {false};
             constexpr int LDS_PAIR = CfgBwdC::LDS > CfgDw::LDS ? CfgBwdC::LDS : CfgDw::LDS;
             if (p4_lds_attr(mlp_bwd_pair_group_kernel<true>, LDS_PAIR, &done_[current_device_slot()]) != hipSuccess)
-                return mlp_fail("mlp: cannot raise the LDS limit of mlp_bwd_pair_group_kernel");
+                return fail("mlp: cannot raise the LDS limit of mlp_bwd_pair_group_kernel");
             hipLaunchKernelGGL(mlp_bwd_pair_group_kernel<true>, dim3(4 * n_wg), dim3(512), LDS_PAIR, st, pg, n_wg, cpw, n_dw);
         }
         dgm::prof_end(DGM_STAGE_MLP_BWD_PAIR, st);
@@ -1421,7 +1416,7 @@ int backward_planes_group(const GroupNet* nets, int N, const int n_wg, hipStream
         hipLaunchKernelGGL(mlp_fold_grad_group_kernel, dim3(any_dt ? 3 : 2, tmax, 2), dim3(256), 0, st, fg);
     }
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return mlp_fail(hipGetErrorString(e));
+    if (e != hipSuccess) return fail(hipGetErrorString(e));
     return 0;
 }
 }  // namespace
@@ -1477,7 +1472,7 @@ int dgm_p4_probe(int N, int kind, int iters, int zero, void* stream) {
             hipMalloc((void**)&Bp, 16 * 4 * 256 * 16) != hipSuccess || hipMalloc((void**)&binv, 1024) != hipSuccess ||
             hipMalloc((void**)&bias, 1024) != hipSuccess || hipMalloc((void**)&mask, (size_t)nt * 1024) != hipSuccess ||
             hipMalloc((void**)&partial, (size_t)256 * 256 * 256 * 4) != hipSuccess || hipMalloc((void**)&pdb, (size_t)256 * 8 * 256 * 4) != hipSuccess)
-            return mlp_fail("p4_probe: hipMalloc failed");
+            return fail("p4_probe: hipMalloc failed");
         cap = nt;
     }
     hipLaunchKernelGGL(p4_probe_fill_kernel, dim3(1024), dim3(256), 0, st, (unsigned*)A, rows * 256, 1u, zero);
@@ -1520,10 +1515,10 @@ int dgm_p4_probe(int N, int kind, int iters, int zero, void* stream) {
         } else if (kind == 1) {
             P4_LAUNCH((mlp_dw4_kernel<8, 8, 1024, 512, 1024, 512>), CfgDw::LDS, pl.chunks, st, d)
         } else {
-            if (n_dw <= 0) return mlp_fail("p4_probe: no pair split at this size");
+            if (n_dw <= 0) return fail("p4_probe: no pair split at this size");
             static bool done_[DGM_MAX_DEVICES] = {false};
             constexpr int LDS_PAIR = CfgBwd::LDS > CfgDw::LDS ? CfgBwd::LDS : CfgDw::LDS;
-            if (p4_lds_attr(mlp_bwd_pair_kernel<false>, LDS_PAIR, &done_[current_device_slot()]) != hipSuccess) return mlp_fail("p4_probe: LDS attribute");
+            if (p4_lds_attr(mlp_bwd_pair_kernel<false>, LDS_PAIR, &done_[current_device_slot()]) != hipSuccess) return fail("p4_probe: LDS attribute");
             Dw4Args dp = d;
             dp.tiles_per_chunk = (nt + n_dw - 1) / n_dw;
 #ifdef P4_XCD_REDUCE
@@ -1532,7 +1527,7 @@ int dgm_p4_probe(int N, int kind, int iters, int zero, void* stream) {
                 static float* xp = nullptr;
                 static int gen = 0;
                 if (!xs) {
-                    if (hipMalloc((void**)&xs, 8 * 128) != hipSuccess || hipMalloc((void**)&xp, (size_t)8 * 65536 * 4) != hipSuccess) return mlp_fail("p4_probe: hipMalloc");
+                    if (hipMalloc((void**)&xs, 8 * 128) != hipSuccess || hipMalloc((void**)&xp, (size_t)8 * 65536 * 4) != hipSuccess) return fail("p4_probe: hipMalloc");
                     (void)hipMemsetAsync(xs, 0, 8 * 128, st);
                 }
                 dp.xsync = getenv("DGM_P4_XCD_OFF") ? nullptr : xs, dp.xpartial = xp, dp.xgen = gen++, dp.xchunks = (nt + dp.tiles_per_chunk - 1) / dp.tiles_per_chunk;
@@ -1544,7 +1539,7 @@ int dgm_p4_probe(int N, int kind, int iters, int zero, void* stream) {
         }
     }
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return mlp_fail(hipGetErrorString(e));
+    if (e != hipSuccess) return fail(hipGetErrorString(e));
     return 0;
 }
 #endif
@@ -1577,9 +1572,9 @@ int dgm_mlp_forward_add(const dgm_mlp_params* p, int N, const float* x, const fl
                         int temb_stride, char* workspace, float* out, void* stream) {
     if (check_params(p)) return 1;
     if (N <= 0) return 0;
-    if (!x || !temb || !workspace || !out) return mlp_fail("mlp_forward: NULL pointer");
+    if (!x || !temb || !workspace || !out) return fail("mlp_forward: NULL pointer");
     if (x_add && (g_gemm_mode < 3 || x_add_stride < 3))
-        return mlp_fail("mlp_forward_add: the addend exists in the plane arithmetic only (f16x3p), rows of at least 3 floats");
+        return fail("mlp_forward_add: the addend exists in the plane arithmetic only (f16x3p), rows of at least 3 floats");
     hipStream_t st = (hipStream_t)stream;
     Ws w = carve(workspace, N);
     const int mode = g_gemm_mode;
@@ -1611,7 +1606,7 @@ int dgm_mlp_forward_add(const dgm_mlp_params* p, int N, const float* x, const fl
     hipLaunchKernelGGL(mlp_rows_small_kernel, dim3((N * 4 + 255) / 256), dim3(256), 0, st, N, p->n_out, w.Y[7], p->Wh, 1,
                        MLP_W, p->bh, out, p->n_out, 0);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return mlp_fail(hipGetErrorString(e));
+    if (e != hipSuccess) return fail(hipGetErrorString(e));
     return 0;
 }
 
@@ -1624,17 +1619,17 @@ int dgm_mlp_backward_dx(const dgm_mlp_params* p, int N, const float* dOut, int t
                         float* const* db, float* dWh, float* dbh, float* dtemb, const float* x, float* dX, void* stream) {
     if (check_params(p)) return 1;
     if (N <= 0) return 0;
-    if (!dOut || !workspace || !dW || !db || !dWh || !dbh) return mlp_fail("mlp_backward: NULL pointer");
-    if ((x == nullptr) != (dX == nullptr)) return mlp_fail("mlp_backward: x and dX come together");
+    if (!dOut || !workspace || !dW || !db || !dWh || !dbh) return fail("mlp_backward: NULL pointer");
+    if ((x == nullptr) != (dX == nullptr)) return fail("mlp_backward: x and dX come together");
     const int mode = g_gemm_mode;
     if (dX && (mode < 3 || temb_stride != 0))
-        return mlp_fail("mlp_backward: the gradient w.r.t. the positions exists in the plane arithmetic only (f16x3p, broadcast time row)");
+        return fail("mlp_backward: the gradient w.r.t. the positions exists in the plane arithmetic only (f16x3p, broadcast time row)");
     {
         const int fm = recall_ws_mode(workspace);
         if (fm >= 0 && (fm & 15) != mode)
-            return mlp_fail("mlp_backward: the arithmetic mode changed since the forward pass on this workspace (dgm_mlp_set_gemm)");
+            return fail("mlp_backward: the arithmetic mode changed since the forward pass on this workspace (dgm_mlp_set_gemm)");
         if (fm >= 0 && ((fm & 16) != 0) != ((mode == 3 || mode == 5) && temb_stride == 0))
-            return mlp_fail("mlp_backward: temb_stride differs from the forward pass on this workspace");
+            return fail("mlp_backward: temb_stride differs from the forward pass on this workspace");
     }
     hipStream_t st = (hipStream_t)stream;
     Ws w = carve(workspace, N);
@@ -1689,18 +1684,18 @@ int dgm_mlp_backward_dx(const dgm_mlp_params* p, int N, const float* dOut, int t
         hipLaunchKernelGGL(mlp_dtemb_bcast_kernel, dim3(p->t_dim), dim3(256), 0, st, p->t_dim, db[0], p->W[0], layer_in(p, 0),
                            db[p->skip_layer], p->W[p->skip_layer], layer_in(p, p->skip_layer), dtemb);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return mlp_fail(hipGetErrorString(e));
+    if (e != hipSuccess) return fail(hipGetErrorString(e));
     return 0;
 }
 
 int dgm_mlp_backward_group(const dgm_mlp_backward_job* a, const dgm_mlp_backward_job* b, int N, int temb_stride, void* stream) {
-    if (!a || !b) return mlp_fail("mlp_backward_group: NULL job");
+    if (!a || !b) return fail("mlp_backward_group: NULL job");
     const dgm_mlp_backward_job* jobs[2] = {a, b};
     if (check_params(a->params) || check_params(b->params)) return 1;
     if (N <= 0) return 0;
     for (const dgm_mlp_backward_job* j : jobs)
-        if (!j->dOut || !j->workspace || !j->dWh || !j->dbh) return mlp_fail("mlp_backward_group: NULL pointer");
-    if (a->workspace == b->workspace) return mlp_fail("mlp_backward_group: the two networks need workspaces of their own");
+        if (!j->dOut || !j->workspace || !j->dWh || !j->dbh) return fail("mlp_backward_group: NULL pointer");
+    if (a->workspace == b->workspace) return fail("mlp_backward_group: the two networks need workspaces of their own");
     const int mode = g_gemm_mode;
     const int fa = recall_ws_mode(a->workspace), fb = recall_ws_mode(b->workspace);
     const int n_wg = p4_group_split(N);
@@ -1715,7 +1710,7 @@ int dgm_mlp_backward_group(const dgm_mlp_backward_job* a, const dgm_mlp_backward
     for (int i = 0; i < 2; i++) {
         const dgm_mlp_backward_job* j = jobs[i];
         for (int l = 0; l < 8; l++)
-            if (!j->dW[l] || !j->db[l]) return mlp_fail("mlp_backward_group: NULL gradient pointer");
+            if (!j->dW[l] || !j->db[l]) return fail("mlp_backward_group: NULL gradient pointer");
         nets[i].p = j->params, nets[i].dOut = j->dOut, nets[i].w = carve(j->workspace, N);
         nets[i].dW = j->dW, nets[i].db = j->db, nets[i].dWh = j->dWh, nets[i].dbh = j->dbh, nets[i].dtemb = j->dtemb;
     }
@@ -1724,25 +1719,25 @@ int dgm_mlp_backward_group(const dgm_mlp_backward_job* a, const dgm_mlp_backward
 
 int dgm_timenet_forward(const float* t, int n_freq, const float* W1, const float* b1, int hidden, const float* W2,
                         const float* b2, int n_out, float* save, float* out, void* stream) {
-    if (!t || !W1 || !b1 || !W2 || !b2 || !save || !out) return mlp_fail("timenet_forward: NULL pointer");
+    if (!t || !W1 || !b1 || !W2 || !b2 || !save || !out) return fail("timenet_forward: NULL pointer");
     if (n_freq < 0 || 2 * n_freq + 1 > 64 || hidden < 1 || hidden > 1024 || n_out < 1 || n_out > 64)
-        return mlp_fail("timenet_forward: unsupported size (2 n_freq + 1 <= 64, hidden <= 1024, n_out <= 64)");
+        return fail("timenet_forward: unsupported size (2 n_freq + 1 <= 64, hidden <= 1024, n_out <= 64)");
     hipLaunchKernelGGL(mlp_timenet_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, t, n_freq, W1, b1, hidden, W2, b2,
                        n_out, save, out);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return mlp_fail(hipGetErrorString(e));
+    if (e != hipSuccess) return fail(hipGetErrorString(e));
     return 0;
 }
 
 int dgm_timenet_backward(const float* d_out, int n_freq, const float* W2, int hidden, int n_out, const float* save,
                          float* dW1, float* db1, float* dW2, float* db2, void* stream) {
-    if (!d_out || !W2 || !save || !dW1 || !db1 || !dW2 || !db2) return mlp_fail("timenet_backward: NULL pointer");
+    if (!d_out || !W2 || !save || !dW1 || !db1 || !dW2 || !db2) return fail("timenet_backward: NULL pointer");
     if (n_freq < 0 || 2 * n_freq + 1 > 64 || hidden < 1 || hidden > 1024 || n_out < 1 || n_out > 64)
-        return mlp_fail("timenet_backward: unsupported size");
+        return fail("timenet_backward: unsupported size");
     hipLaunchKernelGGL(mlp_timenet_bwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, d_out, n_freq, W2, hidden, n_out,
                        save, dW1, db1, dW2, db2);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return mlp_fail(hipGetErrorString(e));
+    if (e != hipSuccess) return fail(hipGetErrorString(e));
     return 0;
 }
 

@@ -18,13 +18,9 @@
 #include <float.h>
 #include <math.h>
 
-#include "dgm_common.hpp"
+#include "dgm_host.hpp"
 
 #pragma clang fp contract(off)
-
-namespace dgm {
-void set_last_error(const char* msg);
-}  // namespace dgm
 
 namespace {
 using namespace dgm;
@@ -36,16 +32,7 @@ constexpr int BBOX_GROUP = 4;                            // rows per thread and 
 constexpr int SCAN_ITEMS = 16;                           // consecutive faces per thread
 constexpr int SCAN_TILE = NI_THREADS * SCAN_ITEMS;       // faces per workgroup
 
-unsigned blocks(long long n, int t = NI_THREADS) { return (unsigned)((n + t - 1) / t); }
 
-int nfail(const char* m) {
-    set_last_error(m);
-    return 1;
-}
-int ndone() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : nfail(hipGetErrorString(e));
-}
 
 // ---- bounding box --------------------------------------------------------------------------------------------------------------
 // (the comparisons are false for a NaN `a`, so a NaN that got in stays; a NaN `b` always gets in.  -0 counts as less than +0, so
@@ -330,8 +317,8 @@ extern "C" {
 size_t dgm_ninit_bbox_scratch_bytes(void) { return 256 + (size_t)BBOX_MAX_BLOCKS * 6 * 4 + 256; }
 
 int dgm_ninit_bbox(int P, const float* xyz, const float* d_xyz, char* scratch, float* out6, void* stream) {
-    if (P <= 0) return nfail("ninit_bbox: need P >= 1 (the extrema of an empty set do not exist)");
-    if (!xyz || !scratch || !out6) return nfail("ninit_bbox: NULL pointer");
+    if (P <= 0) return fail("ninit_bbox: need P >= 1 (the extrema of an empty set do not exist)");
+    if (!xyz || !scratch || !out6) return fail("ninit_bbox: NULL pointer");
     char* base = align_ptr(scratch);
     unsigned* arrive = (unsigned*)base;
     float* partial = (float*)(base + 256);
@@ -344,15 +331,15 @@ int dgm_ninit_bbox(int P, const float* xyz, const float* d_xyz, char* scratch, f
     else
         hipLaunchKernelGGL(bbox_kernel<false>, dim3((unsigned)nb), dim3(NI_THREADS), 0, (hipStream_t)stream, P, xyz, d_xyz, partial, arrive,
                            out6);
-    return ndone();
+    return launch_status();
 }
 
 int dgm_ninit_face_areas(int V, int F, const float* verts, const int* faces, float* area, void* stream) {
-    if (V < 0 || F < 0) return nfail("ninit_face_areas: need V >= 0 and F >= 0");
+    if (V < 0 || F < 0) return fail("ninit_face_areas: need V >= 0 and F >= 0");
     if (F == 0) return 0;
-    if (!faces || !area || (V > 0 && !verts)) return nfail("ninit_face_areas: NULL pointer");
+    if (!faces || !area || (V > 0 && !verts)) return fail("ninit_face_areas: NULL pointer");
     hipLaunchKernelGGL(face_area_kernel, dim3(blocks(F)), dim3(NI_THREADS), 0, (hipStream_t)stream, V, F, verts, faces, area);
-    return ndone();
+    return launch_status();
 }
 
 size_t dgm_ninit_scan_scratch_bytes(int F) {
@@ -362,9 +349,9 @@ size_t dgm_ninit_scan_scratch_bytes(int F) {
 }
 
 int dgm_ninit_area_scan(int F, const float* area, char* scratch, double* cum, void* stream) {
-    if (F < 0) return nfail("ninit_area_scan: need F >= 0");
+    if (F < 0) return fail("ninit_area_scan: need F >= 0");
     if (F == 0) return 0;
-    if (!area || !scratch || !cum) return nfail("ninit_area_scan: NULL pointer");
+    if (!area || !scratch || !cum) return fail("ninit_area_scan: NULL pointer");
     hipStream_t st = (hipStream_t)stream;
     const int nb = scan_blocks(F);
     char* base = align_ptr(scratch);
@@ -373,17 +360,17 @@ int dgm_ninit_area_scan(int F, const float* area, char* scratch, double* cum, vo
     hipLaunchKernelGGL(scan_totals_kernel, dim3(nb), dim3(NI_THREADS), 0, st, (long long)F, area, tile_total);
     hipLaunchKernelGGL(scan_offsets_kernel, dim3(1), dim3(NI_THREADS), 0, st, nb, (const double*)tile_total, tile_off);
     hipLaunchKernelGGL(scan_emit_kernel, dim3(nb), dim3(NI_THREADS), 0, st, (long long)F, area, (const double*)tile_off, cum);
-    return ndone();
+    return launch_status();
 }
 
 int dgm_ninit_sample(int V, int F, int count, const float* verts, const int* faces, const double* cum, const float* u, float* points,
                      int* face_index, void* stream) {
-    if (V < 0 || F < 1 || count < 0) return nfail("ninit_sample: need V >= 0, F >= 1 and count >= 0");
+    if (V < 0 || F < 1 || count < 0) return fail("ninit_sample: need V >= 0, F >= 1 and count >= 0");
     if (count == 0) return 0;
-    if (!faces || !cum || !u || !points || !face_index || (V > 0 && !verts)) return nfail("ninit_sample: NULL pointer");
+    if (!faces || !cum || !u || !points || !face_index || (V > 0 && !verts)) return fail("ninit_sample: NULL pointer");
     hipLaunchKernelGGL(sample_kernel, dim3(blocks(count)), dim3(NI_THREADS), 0, (hipStream_t)stream, V, F, count, verts, faces, cum, u,
                        points, face_index);
-    return ndone();
+    return launch_status();
 }
 
 }  // extern "C"

@@ -14,7 +14,6 @@
 #include "dgm_common.hpp"
 
 namespace dgm {
-void set_last_error(const char* msg);  // c_api.hip
 
 __global__ void __launch_bounds__(256)
 opacity_field_prep_kernel(int P, const float* __restrict__ xyz, const float* __restrict__ rot, const float* __restrict__ scale,

@@ -12,7 +12,6 @@
 #include "dgm_common.hpp"
 
 namespace dgm {
-void set_last_error(const char* msg);  // c_api.hip
 
 static constexpr int ADAM_MAX = 64;      // tensors per launch
 static constexpr int ADAM_CHUNK = 4096;  // elements per block

@@ -23,7 +23,6 @@
 
 namespace dgm {
 
-void set_last_error(const char* msg);  // c_api.hip
 
 static constexpr int RS_ROWS = 4;        // rows (= waves) per block
 static constexpr int RS_PRECISION = 22;  // Pillow's PRECISION_BITS for 8-bit channels

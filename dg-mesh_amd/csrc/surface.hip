@@ -28,7 +28,7 @@
 //     the same: measured and asserted by tests/test_surface_host.py).  Cell edge c = max(1.001 sqrt(max_d2), 1.001 E, 2^-20 extent), E = the largest box edge of a
 //     candidate face, reduced on the device and read by the later kernels from device memory.  A box then spans at most two cells
 //     per axis: at most 8 references per face (the upper cell is clamped to lower + 1, so the bound holds by construction), and the
-//     scratch is known on the host.  Cell coordinates are taken in fp64 from fp32 values (anchor.hip); a face with fp32
+//     scratch is known on the host.  Cell coordinates are taken in fp64 from fp32 values (mesh_grid.hpp); a face with fp32
 //     dist2 < max_d2 has |p - q| < c on every axis, so q's cell -- one the face is registered in -- is among the 27 around p's.
 //     Inside a bucket a face whose box lies farther from p than the best so far is skipped: the fp32 gap to the box is a lower bound
 //     of the fp32 dist2, rounding included (surf_grid_kernel), so a skipped face can neither win nor tie.
@@ -39,48 +39,21 @@
 #include <float.h>
 #include <math.h>
 
-#include "dgm_common.hpp"
+#include "dgm_host.hpp"
+#include "mesh_grid.hpp"
+#include "mesh_scan.hpp"
 
 #pragma clang fp contract(off)
-
-namespace dgm {
-void launch_scan_blocks(hipStream_t st, int n, const unsigned* in, unsigned* out, unsigned* total);
-size_t radix_sort_hist_words(int n);
-const unsigned* radix_sort_pairs(hipStream_t st, int n, int passes, unsigned* keysA, unsigned* valsA, unsigned* keysB,
-                                 unsigned* valsB, unsigned* hist, unsigned* scanned);
-void set_last_error(const char* msg);
-}  // namespace dgm
 
 namespace {
 using namespace dgm;
 
 constexpr int SF_THREADS = 256;
-constexpr int SCAN_ITEMS = 16;                      // consecutive elements per thread in the block scans
-constexpr int SCAN_TILE = SF_THREADS * SCAN_ITEMS;  // elements per scan workgroup
-constexpr int BF_TILE = 256;                        // faces per LDS tile of the brute force
+constexpr int BF_TILE = 256;  // faces per LDS tile of the brute force
 constexpr int BOX_PARTS = 128;
 constexpr int REFS_PER_FACE = 8;
-constexpr double CELL_LIMIT = 1048576.0;            // cells per axis at most (2^20)
-constexpr int CELL_CLAMP = (1 << 20) + 3;
 constexpr unsigned QUERY_MASK = 0xFFFFu;            // buckets of the queries' visiting order (two radix passes)
 constexpr float BOX_PAD = 1.9073486328125e-06f;     // 2^-19
-
-unsigned blocks(long long n, int t = SF_THREADS) { return (unsigned)((n + t - 1) / t); }
-
-int sfail(const char* m) {
-    set_last_error(m);
-    return 1;
-}
-int sdone() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : sfail(hipGetErrorString(e));
-}
-
-size_t pow2_at_least(size_t n) {
-    size_t h = 64;
-    while (h < n) h <<= 1;
-    return h;
-}
 
 // ---- the pair arithmetic (file header) ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ float dot3(float x0, float x1, float x2, float y0, float y1, float y2) { return (x0 * y0 + x1 * y1) + x2 * y2; }
@@ -219,11 +192,6 @@ surf_none_kernel(int N, int* __restrict__ face, float* __restrict__ d2out, float
 }
 
 // ---- the grid over the faces ------------------------------------------------------------------------------------------------------------
-struct GridParams {
-    double origin[3];
-    double inv;  // 1 / cell edge
-};
-
 // the widened box of a candidate face (file header)
 __device__ __forceinline__ void face_box(const float4 A, const float4 B, const float4 C, float lo[3], float hi[3]) {
     const float a[3] = {A.x, A.y, A.z}, b[3] = {B.x, B.y, B.z}, c[3] = {C.x, C.y, C.z};
@@ -256,73 +224,22 @@ face_prep_kernel(int V, int F, const float* __restrict__ verts, const int* __res
 }
 
 // per workgroup: (min lo) x 3, (max hi) x 3, the largest box edge
-__global__ void __launch_bounds__(256) box_partial_kernel(int F, const float4* __restrict__ tri, float* __restrict__ partial) {
-    __shared__ float red[7][256];
-    float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX}, edge = 0.f;
-    for (long long f = (long long)blockIdx.x * 256 + threadIdx.x; f < F; f += (long long)gridDim.x * 256) {
+__global__ void __launch_bounds__(BOX_THREADS) box_partial_kernel(int F, const float4* __restrict__ tri, float* __restrict__ partial) {
+    float v[7];
+    box_start<7>(v);
+    for (long long f = (long long)blockIdx.x * 256 + threadIdx.x; f < F; f += (long long)gridDim.x * 256) {  // ends at F
         const float4 A = tri[3 * f];
         if (A.w == 0.f) continue;
         float lo[3], hi[3];
         face_box(A, tri[3 * f + 1], tri[3 * f + 2], lo, hi);
 #pragma unroll
         for (int k = 0; k < 3; k++) {
-            mn[k] = fminf(mn[k], lo[k]);
-            mx[k] = fmaxf(mx[k], hi[k]);
-            edge = fmaxf(edge, hi[k] - lo[k]);
+            v[k] = box_join(k, v[k], lo[k]);
+            v[3 + k] = box_join(3 + k, v[3 + k], hi[k]);
+            v[6] = box_join(6, v[6], hi[k] - lo[k]);
         }
     }
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        red[k][threadIdx.x] = mn[k];
-        red[3 + k][threadIdx.x] = mx[k];
-    }
-    red[6][threadIdx.x] = edge;
-    __syncthreads();
-    for (int off = 128; off >= 1; off >>= 1) {
-        if ((int)threadIdx.x < off) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                red[k][threadIdx.x] = fminf(red[k][threadIdx.x], red[k][threadIdx.x + off]);
-                red[3 + k][threadIdx.x] = fmaxf(red[3 + k][threadIdx.x], red[3 + k][threadIdx.x + off]);
-            }
-            red[6][threadIdx.x] = fmaxf(red[6][threadIdx.x], red[6][threadIdx.x + off]);
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x < 7) partial[blockIdx.x * 7 + threadIdx.x] = red[threadIdx.x][0];
-}
-
-__global__ void grid_params_kernel(int nparts, const float* __restrict__ partial, float max_d2, GridParams* __restrict__ gp) {
-    if (threadIdx.x != 0) return;
-    float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX}, edge = 0.f;
-    for (int b = 0; b < nparts; b++) {
-        for (int a = 0; a < 3; a++) {
-            lo[a] = fminf(lo[a], partial[b * 7 + a]);
-            hi[a] = fmaxf(hi[a], partial[b * 7 + 3 + a]);
-        }
-        edge = fmaxf(edge, partial[b * 7 + 6]);
-    }
-    double ext = 0.0;
-    for (int a = 0; a < 3; a++) {
-        const bool some = lo[a] <= hi[a];  // (no candidate face at all: any origin will do)
-        gp->origin[a] = some ? (double)lo[a] : 0.0;
-        if (some) ext = fmax(ext, (double)hi[a] - (double)lo[a]);
-    }
-    double cell = 1.001 * sqrt((double)max_d2);
-    cell = fmax(cell, 1.001 * (double)edge);
-    cell = fmax(cell, ext / CELL_LIMIT);
-    gp->inv = cell > 0.0 && cell < (double)INFINITY ? 1.0 / cell : 1.0;
-}
-
-__device__ __forceinline__ int cell_coord(float p, double o, double inv) {
-    double u = floor(((double)p - o) * inv);
-    if (!(u >= -2.0)) u = -2.0;  // (NaN included)
-    if (u > (double)CELL_CLAMP) u = (double)CELL_CLAMP;
-    return (int)u;
-}
-
-__device__ __forceinline__ unsigned cell_hash(int ix, int iy, int iz, unsigned mask) {
-    return (((unsigned)ix * 73856093u) ^ ((unsigned)iy * 19349663u) ^ ((unsigned)iz * 83492791u)) & mask;
+    box_reduce_partial<7>(v, partial);
 }
 
 // every cell the box of face f overlaps -> visit(bucket): at most two cells per axis, REFS_PER_FACE in all
@@ -361,52 +278,6 @@ face_scatter_kernel(int F, const float4* __restrict__ tri, const GridParams* __r
         const unsigned at = atomicAdd(&cursor[b], 1u);
         if (at < capacity) refs[at] = (unsigned)f;  // (always: the count pass walked the same cells)
     });
-}
-
-// exclusive scan of cnt[0, H): tile totals, launch_scan_blocks over them, then the elements
-__device__ __forceinline__ unsigned block_exclusive(unsigned v, unsigned* wave_tot, unsigned& total) {
-    const int lane = lane_id(), wv = threadIdx.x >> 6;
-    const unsigned inc = wave_inclusive_scan_u32(v);
-    if (lane == 63) wave_tot[wv] = inc;
-    __syncthreads();
-    unsigned pre = 0u;
-    total = 0u;
-    for (int w = 0; w < SF_THREADS / 64; w++) {
-        const unsigned t = wave_tot[w];
-        if (w < wv) pre += t;
-        total += t;
-    }
-    __syncthreads();
-    return pre + inc - v;
-}
-
-__global__ void __launch_bounds__(SF_THREADS) scan_tiles_kernel(long long n, const unsigned* __restrict__ in, unsigned* __restrict__ tiles) {
-    __shared__ unsigned wave_tot[SF_THREADS / 64];
-    const long long base = (long long)blockIdx.x * SCAN_TILE + (long long)threadIdx.x * SCAN_ITEMS;
-    unsigned s = 0u;
-    for (int k = 0; k < SCAN_ITEMS; k++)
-        if (base + k < n) s += in[base + k];
-    unsigned total;
-    block_exclusive(s, wave_tot, total);
-    if (threadIdx.x == 0) tiles[blockIdx.x] = total;
-}
-
-__global__ void __launch_bounds__(SF_THREADS)
-scan_emit_kernel(long long n, const unsigned* __restrict__ in, const unsigned* __restrict__ tile_offset, unsigned* __restrict__ start,
-                 unsigned* __restrict__ cursor) {
-    __shared__ unsigned wave_tot[SF_THREADS / 64];
-    const long long base = (long long)blockIdx.x * SCAN_TILE + (long long)threadIdx.x * SCAN_ITEMS;
-    unsigned s = 0u;
-    for (int k = 0; k < SCAN_ITEMS; k++)
-        if (base + k < n) s += in[base + k];
-    unsigned total;
-    unsigned pre = block_exclusive(s, wave_tot, total) + tile_offset[blockIdx.x];
-    for (int k = 0; k < SCAN_ITEMS; k++)
-        if (base + k < n) {
-            start[base + k] = pre;
-            cursor[base + k] = pre;
-            pre += in[base + k];
-        }
 }
 
 __global__ void __launch_bounds__(SF_THREADS)
@@ -470,7 +341,7 @@ struct SurfLayout {
 SurfLayout surf_layout(int N, int F) {
     SurfLayout L;
     L.H = pow2_at_least((size_t)F);
-    L.nb = (int)((L.H + SCAN_TILE - 1) / SCAN_TILE);
+    L.nb = scan_tiles((long long)L.H);
     const size_t hw = radix_sort_hist_words(N);
     size_t o = 0;
     auto take = [&](size_t bytes) {
@@ -549,21 +420,21 @@ size_t dgm_surf_closest_scratch_bytes(int N, int F) {
 
 int dgm_surf_closest(int N, int V, int F, const float* points, const float* verts, const int* faces, float max_d2, char* scratch,
                      int* face, float* d2, float* bary, void* stream) {
-    if (N < 0 || V < 0 || F < 0) return sfail("surf_closest: need N >= 0, V >= 0 and F >= 0");
+    if (N < 0 || V < 0 || F < 0) return fail("surf_closest: need N >= 0, V >= 0 and F >= 0");
     if (N == 0) return 0;  // (before any HIP call)
-    if (!points || !face || !d2 || !bary || (F > 0 && !faces) || (F > 0 && V > 0 && !verts)) return sfail("surf_closest: NULL pointer");
+    if (!points || !face || !d2 || !bary || (F > 0 && !faces) || (F > 0 && V > 0 && !verts)) return fail("surf_closest: NULL pointer");
     hipStream_t st = (hipStream_t)stream;
     if (F == 0 || V == 0 || !(max_d2 > 0.f)) {  // nothing can be reported (NaN bound included)
         hipLaunchKernelGGL(surf_none_kernel, dim3(blocks(N)), dim3(SF_THREADS), 0, st, N, face, d2, bary);
-        return sdone();
+        return launch_status();
     }
     if (isinf(max_d2)) {
         hipLaunchKernelGGL(surf_brute_kernel, dim3(blocks(N)), dim3(SF_THREADS), 0, st, N, V, F, points, verts, faces, max_d2, face, d2,
                            bary);
-        return sdone();
+        return launch_status();
     }
-    if (!scratch) return sfail("surf_closest: NULL scratch");
-    if ((long long)F * REFS_PER_FACE > 0x7fffffffLL) return sfail("surf_closest: too many faces for the grid (8 F must stay below 2^31)");
+    if (!scratch) return fail("surf_closest: NULL scratch");
+    if ((long long)F * REFS_PER_FACE > 0x7fffffffLL) return fail("surf_closest: too many faces for the grid (8 F must stay below 2^31)");
     const SurfLayout L = surf_layout(N, F);
     char* base = align_ptr(scratch);
     float* partial = (float*)(base + L.partial);
@@ -575,16 +446,13 @@ int dgm_surf_closest(int N, int V, int F, const float* points, const float* vert
     unsigned *keysA = (unsigned*)(base + L.keysA), *valsA = (unsigned*)(base + L.valsA);
     unsigned *keysB = (unsigned*)(base + L.keysB), *valsB = (unsigned*)(base + L.valsB);
     const unsigned mask = (unsigned)(L.H - 1);
-    if (hipMemsetAsync(cnt, 0, L.H * 4, st) != hipSuccess) return sfail("surf_closest: memset failed");
+    if (hipMemsetAsync(cnt, 0, L.H * 4, st) != hipSuccess) return fail("surf_closest: memset failed");
     hipLaunchKernelGGL(face_prep_kernel, dim3(blocks(F)), dim3(SF_THREADS), 0, st, V, F, verts, faces, tri, box);
     const int nparts = F < BOX_PARTS * 256 ? (F + 255) / 256 : BOX_PARTS;
     hipLaunchKernelGGL(box_partial_kernel, dim3(nparts), dim3(256), 0, st, F, (const float4*)tri, partial);
-    hipLaunchKernelGGL(grid_params_kernel, dim3(1), dim3(64), 0, st, nparts, (const float*)partial, max_d2, gp);
+    hipLaunchKernelGGL(grid_params_kernel<7>, dim3(1), dim3(64), 0, st, nparts, (const float*)partial, max_d2, gp);
     hipLaunchKernelGGL(face_count_kernel, dim3(blocks(F)), dim3(SF_THREADS), 0, st, F, (const float4*)tri, (const GridParams*)gp, mask, cnt);
-    hipLaunchKernelGGL(scan_tiles_kernel, dim3(L.nb), dim3(SF_THREADS), 0, st, (long long)L.H, (const unsigned*)cnt, tiles);
-    launch_scan_blocks(st, L.nb, tiles, tiles + L.nb, start + L.H);
-    hipLaunchKernelGGL(scan_emit_kernel, dim3(L.nb), dim3(SF_THREADS), 0, st, (long long)L.H, (const unsigned*)cnt,
-                       (const unsigned*)(tiles + L.nb), start, cursor);
+    scan_exclusive(st, (long long)L.H, cnt, tiles, tiles + L.nb, start, cursor, true, start + L.H);
     hipLaunchKernelGGL(face_scatter_kernel, dim3(blocks(F)), dim3(SF_THREADS), 0, st, F, (const float4*)tri, (const GridParams*)gp, mask,
                        cursor, (unsigned)((size_t)F * REFS_PER_FACE), refs);
     hipLaunchKernelGGL(query_key_kernel, dim3(blocks(N)), dim3(SF_THREADS), 0, st, N, points, (const GridParams*)gp, keysA, valsA);
@@ -592,28 +460,28 @@ int dgm_surf_closest(int N, int V, int F, const float* points, const float* vert
     hipLaunchKernelGGL(surf_grid_kernel, dim3(blocks(N)), dim3(SF_THREADS), 0, st, N, F, points, order, (const GridParams*)gp, mask,
                        (const unsigned*)start, (const unsigned*)refs, (const float4*)tri, (const float4*)box, max_d2, face,
                        d2, bary);
-    return sdone();
+    return launch_status();
 }
 
 int dgm_surf_interp(int N, int V, int F, int C, const float* attr, const int* faces, const int* face, const float* bary, float fill,
                     float* out, void* stream) {
-    if (N < 0 || V < 0 || F < 0 || C < 1) return sfail("surf_interp: need N >= 0, V >= 0, F >= 0 and C >= 1");
+    if (N < 0 || V < 0 || F < 0 || C < 1) return fail("surf_interp: need N >= 0, V >= 0, F >= 0 and C >= 1");
     if (N == 0) return 0;  // (before any HIP call)
-    if (!face || !bary || !out || (F > 0 && !faces) || (F > 0 && V > 0 && !attr)) return sfail("surf_interp: NULL pointer");
+    if (!face || !bary || !out || (F > 0 && !faces) || (F > 0 && V > 0 && !attr)) return fail("surf_interp: NULL pointer");
     const long long total = (long long)N * C;
     hipLaunchKernelGGL(surf_interp_kernel, dim3(blocks(total)), dim3(SF_THREADS), 0, (hipStream_t)stream, total, V, F, C, attr, faces, face,
                        bary, fill, out);
-    return sdone();
+    return launch_status();
 }
 
 int dgm_corr_palette(int N, const float* xyz, const float* center, const float* scale, int mode, int cells, float* out, void* stream) {
-    if (N < 0) return sfail("corr_palette: need N >= 0");
-    if (mode != 0 && mode != 1) return sfail("corr_palette: mode must be 0 (rgb) or 1 (checker)");
-    if (cells < 1 || cells > 4096) return sfail("corr_palette: cells must be within [1, 4096]");
+    if (N < 0) return fail("corr_palette: need N >= 0");
+    if (mode != 0 && mode != 1) return fail("corr_palette: mode must be 0 (rgb) or 1 (checker)");
+    if (cells < 1 || cells > 4096) return fail("corr_palette: cells must be within [1, 4096]");
     if (N == 0) return 0;  // (before any HIP call)
-    if (!xyz || !center || !scale || !out) return sfail("corr_palette: NULL pointer");
+    if (!xyz || !center || !scale || !out) return fail("corr_palette: NULL pointer");
     hipLaunchKernelGGL(palette_kernel, dim3(blocks(N)), dim3(SF_THREADS), 0, (hipStream_t)stream, N, xyz, center, scale, mode, cells, out);
-    return sdone();
+    return launch_status();
 }
 
 }  // extern "C"

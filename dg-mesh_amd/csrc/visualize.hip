@@ -14,13 +14,9 @@
 // All four are memory-bound with a few dozen flops per element; nothing is staged in LDS.  Compiled without FMA contraction and
 // with correctly rounded / and sqrt (the point splat must land on the pixels mesh_raster.hip's screen mapping gives, and the
 // bytes of compose are checked against a numpy restatement).
-#include "dgm_common.hpp"
+#include "dgm_host.hpp"
 
 #include <math.h>
-
-namespace dgm {
-void set_last_error(const char* msg);  // c_api.hip
-}
 
 using namespace dgm;
 
@@ -31,15 +27,6 @@ constexpr int VZ_MAX_DIM = 16384;  // H, W limit, as the mesh rasterizer: H * W 
 constexpr int VZ_MAX_PANELS = 4;
 constexpr unsigned long long KEY_EMPTY = ~0ull;
 
-int vfail(const char* m) {
-    dgm::set_last_error(m);
-    return 1;
-}
-int vdone() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : vfail(hipGetErrorString(e));
-}
-unsigned blocks(long long n) { return (unsigned)((n + VZ_THREADS - 1) / VZ_THREADS); }
 
 __device__ __forceinline__ bool face_in_range(const int* __restrict__ tri, int f, int V, int (&v)[3]) {
 #pragma unroll
@@ -222,25 +209,25 @@ bool vz_dims(int H, int W) { return H > 0 && W > 0 && H <= VZ_MAX_DIM && W <= VZ
 extern "C" {
 
 int dgm_vertex_normals(int V, int F, const float* verts, const int* faces, float* normals, void* stream) {
-    if (V < 0 || F < 0) return vfail("vertex_normals: need V >= 0 and F >= 0");
-    if ((V > 0 && (!verts || !normals)) || (F > 0 && !faces)) return vfail("vertex_normals: NULL pointer");
-    if (V == 0) return vdone();
+    if (V < 0 || F < 0) return fail("vertex_normals: need V >= 0 and F >= 0");
+    if ((V > 0 && (!verts || !normals)) || (F > 0 && !faces)) return fail("vertex_normals: NULL pointer");
+    if (V == 0) return launch_status();
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(normals, 0, (size_t)V * 3 * sizeof(float), st) != hipSuccess) return vfail("vertex_normals: memset failed");
+    if (hipMemsetAsync(normals, 0, (size_t)V * 3 * sizeof(float), st) != hipSuccess) return fail("vertex_normals: memset failed");
     if (F > 0) {
         hipLaunchKernelGGL(normals_scatter_kernel, dim3(blocks(F)), dim3(VZ_THREADS), 0, st, V, F, verts, faces, normals);
         hipLaunchKernelGGL(normals_normalize_kernel, dim3(blocks(V)), dim3(VZ_THREADS), 0, st, V, normals);
     }
-    return vdone();
+    return launch_status();
 }
 
 int dgm_mesh_shade(int V, int F, int H, int W, const float* verts, const float* normals, const int* faces, const float* rast,
                    const dgm_shade_params* params, float* image, void* stream) {
-    if (V < 0 || F < 0 || !vz_dims(H, W)) return vfail("mesh_shade: need V >= 0, F >= 0 and 0 < H, W <= 16384");
-    if (!rast || !params || !image || (V > 0 && (!verts || !normals)) || (F > 0 && !faces)) return vfail("mesh_shade: NULL pointer");
+    if (V < 0 || F < 0 || !vz_dims(H, W)) return fail("mesh_shade: need V >= 0, F >= 0 and 0 < H, W <= 16384");
+    if (!rast || !params || !image || (V > 0 && (!verts || !normals)) || (F > 0 && !faces)) return fail("mesh_shade: NULL pointer");
     hipLaunchKernelGGL(shade_kernel, dim3(blocks((long long)H * W)), dim3(VZ_THREADS), 0, (hipStream_t)stream, V, F, H * W, verts, normals,
                        faces, (const float4*)rast, params, image);
-    return vdone();
+    return launch_status();
 }
 
 size_t dgm_point_splat_scratch_bytes(int H, int W) {
@@ -249,36 +236,36 @@ size_t dgm_point_splat_scratch_bytes(int H, int W) {
 
 int dgm_point_splat(int N, int H, int W, const float* pos_clip, const float* colors, int size, const float* bg_color6, char* scratch,
                     float* image, void* stream) {
-    if (N < 0 || !vz_dims(H, W)) return vfail("point_splat: need N >= 0 and 0 < H, W <= 16384");
-    if (size < 1 || size > 15 || !(size & 1)) return vfail("point_splat: size must be odd, 1 to 15");
-    if (!bg_color6 || !scratch || !image || (N > 0 && !pos_clip)) return vfail("point_splat: NULL pointer");
+    if (N < 0 || !vz_dims(H, W)) return fail("point_splat: need N >= 0 and 0 < H, W <= 16384");
+    if (size < 1 || size > 15 || !(size & 1)) return fail("point_splat: size must be odd, 1 to 15");
+    if (!bg_color6 || !scratch || !image || (N > 0 && !pos_clip)) return fail("point_splat: NULL pointer");
     hipStream_t st = (hipStream_t)stream;
     unsigned long long* keys = (unsigned long long*)scratch;
-    if (hipMemsetAsync(keys, 0xff, (size_t)H * W * sizeof(unsigned long long), st) != hipSuccess) return vfail("point_splat: memset failed");
+    if (hipMemsetAsync(keys, 0xff, (size_t)H * W * sizeof(unsigned long long), st) != hipSuccess) return fail("point_splat: memset failed");
     if (N > 0)
         hipLaunchKernelGGL(splat_points_kernel, dim3(blocks(N)), dim3(VZ_THREADS), 0, st, N, H, W, size / 2, (const float4*)pos_clip, keys);
     SplatColors sc;
     for (int c = 0; c < 3; c++) sc.bg[c] = bg_color6[c], sc.uniform[c] = bg_color6[3 + c];
     hipLaunchKernelGGL(splat_resolve_kernel, dim3(blocks((long long)H * W)), dim3(VZ_THREADS), 0, st, N, H * W,
                        (const unsigned long long*)keys, colors, sc, image);
-    return vdone();
+    return launch_status();
 }
 
 int dgm_compose_frame(int n_panels, const float* const* panels, const int* layouts, int H, int W, int downsample, unsigned char* out_u8,
                       void* stream) {
-    if (n_panels < 1 || n_panels > VZ_MAX_PANELS) return vfail("compose_frame: 1 to 4 panels");
-    if (!vz_dims(H, W) || (downsample != 1 && downsample != 2)) return vfail("compose_frame: need 0 < H, W <= 16384 and downsample 1 or 2");
-    if (downsample == 2 && ((H | W) & 1)) return vfail("compose_frame: downsample 2 needs even H and W");
-    if (!panels || !layouts || !out_u8) return vfail("compose_frame: NULL pointer");
+    if (n_panels < 1 || n_panels > VZ_MAX_PANELS) return fail("compose_frame: 1 to 4 panels");
+    if (!vz_dims(H, W) || (downsample != 1 && downsample != 2)) return fail("compose_frame: need 0 < H, W <= 16384 and downsample 1 or 2");
+    if (downsample == 2 && ((H | W) & 1)) return fail("compose_frame: downsample 2 needs even H and W");
+    if (!panels || !layouts || !out_u8) return fail("compose_frame: NULL pointer");
     Panels pn;
     for (int k = 0; k < VZ_MAX_PANELS; k++) {
         pn.ptr[k] = k < n_panels ? panels[k] : nullptr;
         pn.hwc[k] = k < n_panels ? layouts[k] : 0;
-        if (k < n_panels && (!pn.ptr[k] || (pn.hwc[k] != 0 && pn.hwc[k] != 1))) return vfail("compose_frame: NULL panel or a layout other than 0 / 1");
+        if (k < n_panels && (!pn.ptr[k] || (pn.hwc[k] != 0 && pn.hwc[k] != 1))) return fail("compose_frame: NULL panel or a layout other than 0 / 1");
     }
     const long long n = (long long)(H / downsample) * (W / downsample) * n_panels;
     hipLaunchKernelGGL(compose_kernel, dim3(blocks(n)), dim3(VZ_THREADS), 0, (hipStream_t)stream, pn, n_panels, H, W, downsample, out_u8);
-    return vdone();
+    return launch_status();
 }
 
 }  // extern "C"

@@ -15,16 +15,11 @@ Conventions chosen here (diso is not vendored, so they are this project's, not c
   * vertices are ordered by (owning grid point, axis), faces by (cell, case-table order): the output is identical run to run.
 One host synchronisation per forward: the 8-byte read-back of {V, F} that sizes the outputs.
 """
-import ctypes
 
 import torch
 import torch.nn as nn
 
 from . import _lib
-
-
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else ctypes.c_void_p(0)
 
 
 def _st():
@@ -56,12 +51,12 @@ class _MarchingCubes(torch.autograd.Function):
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         counts = torch.empty(2, dtype=torch.int32, device=dev)
         with _lib.device_guard(dev):
-            _lib.check(L.dgm_mc_count(X, Y, Z, _vp(grid), float(iso), _vp(scratch), _vp(counts), _st()))
+            _lib.check(L.dgm_mc_count(X, Y, Z, _lib.vp(grid), float(iso), _lib.vp(scratch), _lib.vp(counts), _st()))
             V, F = counts.tolist()  # the one host synchronisation: the output sizes
             verts = torch.empty((V, 3), dtype=torch.float32, device=dev)
             faces = torch.empty((F, 3), dtype=torch.int32, device=dev)
-            _lib.check(L.dgm_mc_emit(X, Y, Z, _vp(grid), _vp(deform), float(iso), int(bool(normalize)), _vp(scratch), V, F,
-                                     _vp(verts), _vp(faces), _st()))
+            _lib.check(L.dgm_mc_emit(X, Y, Z, _lib.vp(grid), _lib.vp(deform), float(iso), int(bool(normalize)), _lib.vp(scratch), V, F,
+                                     _lib.vp(verts), _lib.vp(faces), _st()))
         ctx.save_for_backward(grid, deform, scratch)
         ctx.iso, ctx.normalize, ctx.V = float(iso), bool(normalize), V
         ctx.mark_non_differentiable(faces)
@@ -76,8 +71,8 @@ class _MarchingCubes(torch.autograd.Function):
         dgrid = torch.empty_like(grid)
         ddeform = torch.empty_like(deform) if deform is not None else None
         with _lib.device_guard(grid.device):
-            _lib.check(_lib.lib().dgm_mc_backward(X, Y, Z, _vp(grid), _vp(deform), ctx.iso, int(ctx.normalize), _vp(scratch), ctx.V,
-                                                  _vp(dverts), _vp(dgrid), _vp(ddeform), _st()))
+            _lib.check(_lib.lib().dgm_mc_backward(X, Y, Z, _lib.vp(grid), _lib.vp(deform), ctx.iso, int(ctx.normalize), _lib.vp(scratch), ctx.V,
+                                                  _lib.vp(dverts), _lib.vp(dgrid), _lib.vp(ddeform), _st()))
         return dgrid, ddeform, None, None
 
 

@@ -13,7 +13,6 @@ Definitions (this project's; include/dgmesh_hip.h states them for the C ABI):
 Everything is integers, comparisons and copies: the results are bit-reproducible.  fp32 vertices, int32 faces, CUDA/HIP tensors only
 -- no CPU fallback.  Host synchronisations: 8 bytes in connected_components (the count of out-of-range faces, which raises), 8 bytes
 in clean_mesh (the output sizes)."""
-import ctypes
 from dataclasses import dataclass
 
 import torch
@@ -44,14 +43,6 @@ def as_spec(clean):
     if isinstance(clean, dict):
         return CleanSpec(**clean)
     raise TypeError(f"mesh_clean: clean must be None, a CleanSpec or a dict of its fields, got {type(clean).__name__}")
-
-
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else ctypes.c_void_p(0)
-
-
-def _scratch(nbytes, dev):
-    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
 
 
 def tile():
@@ -92,9 +83,9 @@ def connected_components(faces, num_verts):
     dev = faces.device
     labels = torch.empty(V, dtype=torch.int32, device=dev)
     info = torch.empty(2, dtype=torch.int32, device=dev)
-    scratch = _scratch(L.dgm_mesh_cc_scratch_bytes(V, F), dev)
+    scratch = _lib.scratch(L.dgm_mesh_cc_scratch_bytes(V, F), dev)
     with _lib.device_guard(dev):
-        _lib.check(L.dgm_mesh_cc_label(V, F, _vp(faces), _vp(scratch), _vp(labels), _vp(info), _lib.stream_ptr()))
+        _lib.check(L.dgm_mesh_cc_label(V, F, _lib.vp(faces), _lib.vp(scratch), _lib.vp(labels), _lib.vp(info), _lib.stream_ptr()))
         bad = int(info[0])  # host synchronisation
     if bad:
         raise ValueError(f"mesh_clean.connected_components: {bad} of {F} faces have an index outside [0, {V})")
@@ -108,7 +99,7 @@ def _stats(verts, faces, labels):
     comp_verts = torch.empty(V, dtype=torch.int32, device=dev)
     comp_bbox = torch.empty((V, 6), dtype=torch.float32, device=dev)
     with _lib.device_guard(dev):
-        _lib.check(L.dgm_mesh_cc_stats(V, F, _vp(verts), _vp(faces), _vp(labels), _vp(comp_faces), _vp(comp_verts), _vp(comp_bbox),
+        _lib.check(L.dgm_mesh_cc_stats(V, F, _lib.vp(verts), _lib.vp(faces), _lib.vp(labels), _lib.vp(comp_faces), _lib.vp(comp_verts), _lib.vp(comp_bbox),
                                        _lib.stream_ptr()))
     return comp_faces, comp_verts, comp_bbox
 
@@ -145,10 +136,10 @@ def keep_mask(verts, faces, labels=None, *, largest=False, min_faces=0, min_diam
     labels = connected_components(faces, V) if labels is None else _labels("keep_mask", labels, V, dev)
     comp_faces, comp_verts, comp_bbox = _stats(verts, faces, labels)
     keep = torch.empty(F, dtype=torch.uint8, device=dev)
-    scratch = _scratch(L.dgm_mesh_cc_select_scratch_bytes(), dev)
+    scratch = _lib.scratch(L.dgm_mesh_cc_select_scratch_bytes(), dev)
     with _lib.device_guard(dev):
-        _lib.check(L.dgm_mesh_cc_select(V, F, _vp(faces), _vp(labels), _vp(comp_faces), _vp(comp_verts), _vp(comp_bbox),
-                                        int(bool(largest)), int(min_faces), float(min_diameter_frac), _vp(scratch), _vp(keep),
+        _lib.check(L.dgm_mesh_cc_select(V, F, _lib.vp(faces), _lib.vp(labels), _lib.vp(comp_faces), _lib.vp(comp_verts), _lib.vp(comp_bbox),
+                                        int(bool(largest)), int(min_faces), float(min_diameter_frac), _lib.vp(scratch), _lib.vp(keep),
                                         _lib.stream_ptr()))
     return keep
 
@@ -163,17 +154,17 @@ def compact(verts, faces, keep):
         raise ValueError(f"mesh_clean.compact: keep must be ({F},) uint8 or bool on {dev}")
     keep = keep.contiguous().view(torch.uint8)
     L = _lib.lib()
-    scratch = _scratch(L.dgm_mesh_compact_scratch_bytes(V, F), dev)
+    scratch = _lib.scratch(L.dgm_mesh_compact_scratch_bytes(V, F), dev)
     counts = torch.empty(2, dtype=torch.int32, device=dev)
     with _lib.device_guard(dev):
-        _lib.check(L.dgm_mesh_compact_count(V, F, _vp(faces), _vp(keep), _vp(scratch), _vp(counts), _lib.stream_ptr()))
+        _lib.check(L.dgm_mesh_compact_count(V, F, _lib.vp(faces), _lib.vp(keep), _lib.vp(scratch), _lib.vp(counts), _lib.stream_ptr()))
         Vn, Fn = counts.tolist()  # the one host synchronisation: the output sizes
         verts_out = torch.empty((Vn, 3), dtype=torch.float32, device=dev)
         faces_out = torch.empty((Fn, 3), dtype=torch.int32, device=dev)
         vert_index = torch.empty(Vn, dtype=torch.int32, device=dev)
         face_index = torch.empty(Fn, dtype=torch.int32, device=dev)
-        _lib.check(L.dgm_mesh_compact_emit(V, F, _vp(verts), _vp(faces), _vp(scratch), Vn, Fn, _vp(verts_out), _vp(faces_out),
-                                           _vp(vert_index), _vp(face_index), _lib.stream_ptr()))
+        _lib.check(L.dgm_mesh_compact_emit(V, F, _lib.vp(verts), _lib.vp(faces), _lib.vp(scratch), Vn, Fn, _lib.vp(verts_out), _lib.vp(faces_out),
+                                           _lib.vp(vert_index), _lib.vp(face_index), _lib.stream_ptr()))
     return verts_out, faces_out, vert_index, face_index
 
 

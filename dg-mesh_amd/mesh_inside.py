@@ -18,7 +18,6 @@ float32 / int32 CUDA/HIP tensors only -- no CPU fallback; anything else raises.
   python -m dgmesh_amd.mesh_inside a.ply b.ply [--points N] [--seed S]
 prints one JSON line: the volume IoU of the two mesh PLYs, the counts and the two volumes."""
 import argparse
-import ctypes
 import json
 import math
 
@@ -28,10 +27,6 @@ from . import _lib
 
 SCRATCH_LIMIT = 64 << 20  # bytes of slice sums per launch; more queries are taken in batches (the result does not depend on them)
 SLICE_FACES = 16384       # WN_SLICE of csrc/mesh_inside.hip
-
-
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else None
 
 
 def _need(name, t, what, dtype):
@@ -76,7 +71,7 @@ def winding_number(points, verts, faces):
         for at in range(0, N, step):
             n = min(step, N - at)
             scratch = torch.empty(int(L.dgm_wind_scratch_bytes(n, F)), dtype=torch.uint8, device=p.device)
-            _lib.check(L.dgm_wind_number(n, V, F, _vp(p[at:at + n]), _vp(v), _vp(f), _vp(scratch), _vp(w[at:at + n]), _lib.stream_ptr()))
+            _lib.check(L.dgm_wind_number(n, V, F, _lib.vp(p[at:at + n]), _lib.vp(v), _lib.vp(f), _lib.vp(scratch), _lib.vp(w[at:at + n]), _lib.stream_ptr()))
     return w
 
 

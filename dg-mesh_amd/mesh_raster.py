@@ -44,15 +44,10 @@ that costs nothing):
 Not provided: MSAA, mip-maps (uv_da, mip_level_bias, mip, max_mip_level, the linear-mipmap filters: they need rast_db), cube maps,
 rast_db, depth peeling, range mode, batches larger than 1.
 """
-import ctypes
 
 import torch
 
 from . import _lib
-
-
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else ctypes.c_void_p(0)
 
 
 def _st():
@@ -100,7 +95,7 @@ class _Rasterize(torch.autograd.Function):
         scratch = torch.empty(int(L.dgm_tri_raster_scratch_bytes(F, H, W)), dtype=torch.uint8, device=dev)
         rast = torch.empty((1, H, W, 4), dtype=torch.float32, device=dev)
         with _lib.device_guard(dev):
-            _lib.check(L.dgm_tri_rasterize_forward(V, F, H, W, _vp(pos), _vp(tri), _vp(scratch), _vp(rast), _st()))
+            _lib.check(L.dgm_tri_rasterize_forward(V, F, H, W, _lib.vp(pos), _lib.vp(tri), _lib.vp(scratch), _lib.vp(rast), _st()))
         ctx.save_for_backward(pos, tri, rast)
         return rast
 
@@ -113,7 +108,7 @@ class _Rasterize(torch.autograd.Function):
         drast = drast.contiguous().float()
         dpos = torch.empty_like(pos)
         with _lib.device_guard(pos.device):
-            _lib.check(_lib.lib().dgm_tri_rasterize_backward(V, F, H, W, _vp(pos), _vp(tri), _vp(rast), _vp(drast), _vp(dpos), _st()))
+            _lib.check(_lib.lib().dgm_tri_rasterize_backward(V, F, H, W, _lib.vp(pos), _lib.vp(tri), _lib.vp(rast), _lib.vp(drast), _lib.vp(dpos), _st()))
         return dpos, None, None, None
 
 
@@ -126,7 +121,7 @@ class _Interpolate(torch.autograd.Function):
         H, W = int(rast.shape[1]), int(rast.shape[2])
         out = torch.empty((1, H, W, C), dtype=torch.float32, device=attr.device)
         with _lib.device_guard(attr.device):
-            _lib.check(L.dgm_tri_interpolate_forward(V, F, H, W, C, _vp(attr), _vp(rast), _vp(tri), _vp(out), _st()))
+            _lib.check(L.dgm_tri_interpolate_forward(V, F, H, W, C, _lib.vp(attr), _lib.vp(rast), _lib.vp(tri), _lib.vp(out), _st()))
         ctx.save_for_backward(attr, rast, tri)
         return out
 
@@ -141,8 +136,8 @@ class _Interpolate(torch.autograd.Function):
         dattr = torch.empty_like(attr)
         drast = torch.empty_like(rast)
         with _lib.device_guard(attr.device):
-            _lib.check(_lib.lib().dgm_tri_interpolate_backward(V, F, H, W, C, _vp(attr), _vp(rast), _vp(tri), _vp(dout), _vp(dattr),
-                                                               _vp(drast), _st()))
+            _lib.check(_lib.lib().dgm_tri_interpolate_backward(V, F, H, W, C, _lib.vp(attr), _lib.vp(rast), _lib.vp(tri), _lib.vp(dout), _lib.vp(dattr),
+                                                               _lib.vp(drast), _st()))
         return dattr, drast, None
 
 
@@ -156,7 +151,7 @@ class _Antialias(torch.autograd.Function):
         scratch = torch.empty(int(L.dgm_tri_aa_scratch_bytes(F)), dtype=torch.uint8, device=dev)
         out = torch.empty_like(color)
         with _lib.device_guard(dev):
-            _lib.check(L.dgm_tri_antialias_forward(V, F, H, W, C, _vp(color), _vp(rast), _vp(pos), _vp(tri), _vp(scratch), _vp(out),
+            _lib.check(L.dgm_tri_antialias_forward(V, F, H, W, C, _lib.vp(color), _lib.vp(rast), _lib.vp(pos), _lib.vp(tri), _lib.vp(scratch), _lib.vp(out),
                                                    _st()))
         ctx.save_for_backward(color, rast, pos, tri, scratch)
         return out
@@ -171,8 +166,8 @@ class _Antialias(torch.autograd.Function):
         dcolor = torch.empty_like(color)
         dpos = torch.empty_like(pos)
         with _lib.device_guard(color.device):
-            _lib.check(_lib.lib().dgm_tri_antialias_backward(V, F, H, W, C, _vp(color), _vp(rast), _vp(pos), _vp(tri), _vp(scratch),
-                                                             _vp(dout), _vp(dcolor), _vp(dpos), _st()))
+            _lib.check(_lib.lib().dgm_tri_antialias_backward(V, F, H, W, C, _lib.vp(color), _lib.vp(rast), _lib.vp(pos), _lib.vp(tri), _lib.vp(scratch),
+                                                             _lib.vp(dout), _lib.vp(dcolor), _lib.vp(dpos), _st()))
         return dcolor, None, dpos, None
 
 
@@ -187,7 +182,7 @@ class _Texture(torch.autograd.Function):
         n = uv.numel() // 2
         out = torch.empty(tuple(uv.shape[:-1]) + (C,), dtype=torch.float32, device=tex.device)
         with _lib.device_guard(tex.device):
-            _lib.check(_lib.lib().dgm_tri_texture_forward(n, Ht, Wt, C, filt, boundary, _vp(tex), _vp(uv), _vp(out), _st()))
+            _lib.check(_lib.lib().dgm_tri_texture_forward(n, Ht, Wt, C, filt, boundary, _lib.vp(tex), _lib.vp(uv), _lib.vp(out), _st()))
         ctx.save_for_backward(tex, uv)
         ctx.modes = (filt, boundary)
         return out
@@ -203,7 +198,7 @@ class _Texture(torch.autograd.Function):
         dtex = torch.empty_like(tex)
         duv = torch.empty_like(uv)
         with _lib.device_guard(tex.device):
-            _lib.check(_lib.lib().dgm_tri_texture_backward(n, Ht, Wt, C, filt, boundary, _vp(tex), _vp(uv), _vp(dout), _vp(dtex), _vp(duv),
+            _lib.check(_lib.lib().dgm_tri_texture_backward(n, Ht, Wt, C, filt, boundary, _lib.vp(tex), _lib.vp(uv), _lib.vp(dout), _lib.vp(dtex), _lib.vp(duv),
                                                            _st()))
         return dtex, duv, None, None
 

@@ -22,7 +22,6 @@ float32 / int32 CUDA/HIP tensors only -- no CPU fallback; anything else raises.
   python -m dgmesh_amd.mesh_ray mesh.ply --ao out.ply [--samples N] [--flip]
 writes the mesh with its vertex ambient occlusion in the vertex colours: the file's colours multiplied by it, grey without any."""
 import argparse
-import ctypes
 import math
 
 import torch
@@ -32,10 +31,6 @@ from . import _lib
 AUTO_MIN_FACES = 752       # accel="auto": the structure from this many faces on, the smallest mesh on which tools/mesh_ray_bench.py
                            # showed build + accelerated cast ahead of the brute force for one 800 x 800 cast
 RAY_BATCH = 1 << 22        # rays per launch of ambient_occlusion (memory only: the result does not depend on it)
-
-
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else None
 
 
 def _need(name, t, what, dtype):
@@ -71,7 +66,7 @@ class RayMesh:
         self.accel = torch.empty(int(L.dgm_ray_accel_bytes(F)), dtype=torch.uint8, device=dev)
         with _lib.device_guard(dev):
             scratch = torch.empty(int(L.dgm_ray_build_scratch_bytes(F)), dtype=torch.uint8, device=dev)
-            _lib.check(L.dgm_ray_build(V, F, _vp(self.verts), _vp(self.faces), _vp(scratch), _vp(self.accel), _lib.stream_ptr()))
+            _lib.check(L.dgm_ray_build(V, F, _lib.vp(self.verts), _lib.vp(self.faces), _lib.vp(scratch), _lib.vp(self.accel), _lib.stream_ptr()))
 
 
 def _resolve(name, verts, faces, accel):
@@ -89,7 +84,7 @@ def _resolve(name, verts, faces, accel):
 
 
 def _accel_ptr(held):
-    return _vp(held.accel) if held is not None else None
+    return _lib.vp(held.accel) if held is not None else None
 
 
 def _rays(name, origins, dirs, v):
@@ -117,8 +112,8 @@ def ray_cast(origins, dirs, verts, faces, t_min=0.0, t_max=math.inf, accel="auto
     t = torch.empty(N, dtype=torch.float32, device=o.device)
     bary = torch.empty((N, 3), dtype=torch.float32, device=o.device)
     with _lib.device_guard(o.device):
-        _lib.check(_lib.lib().dgm_ray_cast(N, v.shape[0], f.shape[0], _vp(o), _vp(d), float(t_min), float(t_max), _vp(v), _vp(f), _accel_ptr(acc),
-                                           _vp(face), _vp(t), _vp(bary), _lib.stream_ptr()))
+        _lib.check(_lib.lib().dgm_ray_cast(N, v.shape[0], f.shape[0], _lib.vp(o), _lib.vp(d), float(t_min), float(t_max), _lib.vp(v), _lib.vp(f), _accel_ptr(acc),
+                                           _lib.vp(face), _lib.vp(t), _lib.vp(bary), _lib.stream_ptr()))
     return face, t, bary
 
 
@@ -130,8 +125,8 @@ def occluded(origins, dirs, verts, faces, t_min=0.0, t_max=math.inf, accel="auto
     N = o.shape[0]
     hit = torch.empty(N, dtype=torch.uint8, device=o.device)
     with _lib.device_guard(o.device):
-        _lib.check(_lib.lib().dgm_ray_occluded(N, v.shape[0], f.shape[0], _vp(o), _vp(d), float(t_min), float(t_max), _vp(v), _vp(f), _accel_ptr(acc),
-                                               _vp(hit), _lib.stream_ptr()))
+        _lib.check(_lib.lib().dgm_ray_occluded(N, v.shape[0], f.shape[0], _lib.vp(o), _lib.vp(d), float(t_min), float(t_max), _lib.vp(v), _lib.vp(f), _accel_ptr(acc),
+                                               _lib.vp(hit), _lib.stream_ptr()))
     return hit != 0
 
 

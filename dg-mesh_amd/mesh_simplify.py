@@ -29,7 +29,6 @@ box and 8 bytes per count-only pass of the bisection, 11 at the most (the pass t
 Command line: python -m dgmesh_amd.mesh_simplify in.ply out.ply (--cell H | --grid G | --target_faces N) [--regularization E]
 reads and writes ply_io's triangle-mesh PLY and keeps vertex colours (a new vertex takes its representative's)."""
 import argparse
-import ctypes
 from dataclasses import dataclass
 
 import numpy as np
@@ -62,14 +61,6 @@ def as_spec(simplify):
     if isinstance(simplify, dict):
         return SimplifySpec(**simplify)
     raise TypeError(f"mesh_simplify: simplify must be None, a SimplifySpec or a dict of its fields, got {type(simplify).__name__}")
-
-
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else ctypes.c_void_p(0)
-
-
-def _scratch(nbytes, dev):
-    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
 
 
 def _mesh(verts, faces):
@@ -122,8 +113,8 @@ class _State:
     """What one count pass leaves on the device and the placement continues from."""
 
     def __init__(self, L, V, F, dev, nbytes):
-        self.scratch = _scratch(nbytes, dev)
-        self.cscratch = _scratch(L.dgm_mesh_compact_scratch_bytes(V, F), dev)
+        self.scratch = _lib.scratch(nbytes, dev)
+        self.cscratch = _lib.scratch(L.dgm_mesh_compact_scratch_bytes(V, F), dev)
         self.rep_faces = torch.empty((F, 3), dtype=torch.int32, device=dev)
         self.keep = torch.empty(F, dtype=torch.uint8, device=dev)
         self.h, self.dims, self.Vn, self.Fn = None, (1, 1, 1), 0, 0
@@ -147,7 +138,7 @@ class _Pass:
         box = torch.empty(6, dtype=torch.float32, device=dev)
         with _lib.device_guard(dev):
             for s in self.states:  # (every state's scratch gets the valid-face and used-vertex marks)
-                _lib.check(L.dgm_mesh_simplify_box(V, F, _vp(verts), _vp(faces), _vp(s.scratch), _vp(box), _lib.stream_ptr()))
+                _lib.check(L.dgm_mesh_simplify_box(V, F, _lib.vp(verts), _lib.vp(faces), _lib.vp(s.scratch), _lib.vp(box), _lib.stream_ptr()))
             self.box = box.cpu().numpy()  # host read-back: 24 bytes
         self.empty = not (self.box[0] <= self.box[3])
         self.count_passes = 0
@@ -163,8 +154,8 @@ class _Pass:
             return 0, 0
         s.dims = grid_dims(self.box, s.h)
         with _lib.device_guard(self.dev):
-            _lib.check(self.L.dgm_mesh_simplify_count(self.V, self.F, _vp(self.verts), _vp(self.faces), *self._grid_args(s), _vp(s.scratch),
-                                                      _vp(s.cscratch), _vp(s.rep_faces), _vp(s.keep), _vp(self.counts), _lib.stream_ptr()))
+            _lib.check(self.L.dgm_mesh_simplify_count(self.V, self.F, _lib.vp(self.verts), _lib.vp(self.faces), *self._grid_args(s), _lib.vp(s.scratch),
+                                                      _lib.vp(s.cscratch), _lib.vp(s.rep_faces), _lib.vp(s.keep), _lib.vp(self.counts), _lib.stream_ptr()))
             self.count_passes += 1
             s.Vn, s.Fn = self.counts.tolist()  # host read-back: the sizes
         return s.Vn, s.Fn
@@ -191,11 +182,11 @@ class _Pass:
         vert_map = torch.empty(V, dtype=torch.int32, device=dev)
         with _lib.device_guard(dev):
             st = _lib.stream_ptr()
-            _lib.check(L.dgm_mesh_simplify_place(V, F, _vp(self.verts), _vp(self.faces), _vp(s.rep_faces), *self._grid_args(s),
-                                                 float(regularization), _vp(s.scratch), _vp(placed), st))
-            _lib.check(L.dgm_mesh_compact_emit(V, F, _vp(placed), _vp(s.rep_faces), _vp(s.cscratch), Vn, Fn, _vp(verts_out),
-                                               _vp(faces_out), _vp(vert_index), _vp(face_index), st))
-            _lib.check(L.dgm_mesh_simplify_vert_map(V, F, Vn, _vp(vert_index), _vp(s.scratch), _vp(vert_map), st))
+            _lib.check(L.dgm_mesh_simplify_place(V, F, _lib.vp(self.verts), _lib.vp(self.faces), _lib.vp(s.rep_faces), *self._grid_args(s),
+                                                 float(regularization), _lib.vp(s.scratch), _lib.vp(placed), st))
+            _lib.check(L.dgm_mesh_compact_emit(V, F, _lib.vp(placed), _lib.vp(s.rep_faces), _lib.vp(s.cscratch), Vn, Fn, _lib.vp(verts_out),
+                                               _lib.vp(faces_out), _lib.vp(vert_index), _lib.vp(face_index), st))
+            _lib.check(L.dgm_mesh_simplify_vert_map(V, F, Vn, _lib.vp(vert_index), _lib.vp(s.scratch), _lib.vp(vert_map), st))
         return verts_out, faces_out, vert_index, face_index, vert_map
 
 

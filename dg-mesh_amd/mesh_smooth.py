@@ -21,7 +21,6 @@ sizes of the edge table).
 Command line: python -m dgmesh_amd.mesh_smooth in.ply out.ply [--iterations N] [--lam L] [--mu M] [--method taubin|laplacian]
 [--boundary fixed|curve|free] reads and writes ply_io's triangle-mesh PLY and keeps vertex colours."""
 import argparse
-import ctypes
 from dataclasses import dataclass
 
 import numpy as np
@@ -53,10 +52,6 @@ def as_spec(smooth):
     if isinstance(smooth, dict):
         return SmoothSpec(**smooth)
     raise TypeError(f"mesh_smooth: smooth must be None, a SmoothSpec or a dict of its fields, got {type(smooth).__name__}")
-
-
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else ctypes.c_void_p(0)
 
 
 def _mesh(verts, faces):
@@ -110,8 +105,8 @@ def smooth_mesh(verts, faces, *, iterations=10, lam=0.5, mu=-0.53, method="taubi
     with _lib.device_guard(dev):
         st = _lib.stream_ptr()
         for f in factors:
-            _lib.check(L.dgm_mesh_smooth_step(V, A, _vp(src), _vp(table.adj_offset), _vp(t["adj"]), _vp(t["adj_kind"]), _vp(table.vert_flag),
-                                              f, BOUNDARIES.index(boundary), _vp(dst), st))
+            _lib.check(L.dgm_mesh_smooth_step(V, A, _lib.vp(src), _lib.vp(table.adj_offset), _lib.vp(t["adj"]), _lib.vp(t["adj_kind"]), _lib.vp(table.vert_flag),
+                                              f, BOUNDARIES.index(boundary), _lib.vp(dst), st))
             src, dst = dst, (spare if src is verts else src)
     return src
 

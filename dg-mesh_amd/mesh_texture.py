@@ -34,7 +34,6 @@ does not light it.
 
 Command line: python -m dgmesh_amd.mesh_texture in.ply out.obj|out.glb (--size N | --cell S) [--ao N] bakes a PLY's vertex colours."""
 import argparse
-import ctypes
 import math
 import os
 from dataclasses import dataclass
@@ -116,10 +115,6 @@ def build_atlas(n_faces, *, size=None, cell=None):
     return Atlas(size, cell, size // cell, F)
 
 
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else ctypes.c_void_p(0)
-
-
 def atlas_uv(atlas, device):
     """The per-corner texture coordinates (F, 3, 2) of the atlas, on `device` (dgm_atlas_uv)."""
     device = torch.device(device)
@@ -127,7 +122,7 @@ def atlas_uv(atlas, device):
         raise RuntimeError("mesh_texture.atlas_uv needs a CUDA/HIP device (dg-mesh_amd has no CPU path)")
     uv = torch.empty((atlas.n_faces, 3, 2), dtype=torch.float32, device=device)
     with _lib.device_guard(device):
-        _lib.check(_lib.lib().dgm_atlas_uv(atlas.n_faces, atlas.size, atlas.cell, _vp(uv), _lib.stream_ptr()))
+        _lib.check(_lib.lib().dgm_atlas_uv(atlas.n_faces, atlas.size, atlas.cell, _lib.vp(uv), _lib.stream_ptr()))
     return uv
 
 
@@ -151,7 +146,7 @@ def atlas_interpolate(atlas, attr, faces):
     out = torch.empty((atlas.size, atlas.size, C), dtype=torch.float32, device=attr.device)
     face_id = torch.empty((atlas.size, atlas.size), dtype=torch.int32, device=attr.device)
     with _lib.device_guard(attr.device):
-        _lib.check(_lib.lib().dgm_atlas_interpolate(V, atlas.n_faces, C, atlas.size, atlas.cell, _vp(attr), _vp(faces), _vp(out), _vp(face_id),
+        _lib.check(_lib.lib().dgm_atlas_interpolate(V, atlas.n_faces, C, atlas.size, atlas.cell, _lib.vp(attr), _lib.vp(faces), _lib.vp(out), _lib.vp(face_id),
                                                     _lib.stream_ptr()))
     return out, face_id
 

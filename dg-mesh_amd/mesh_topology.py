@@ -20,7 +20,6 @@ bytes for the out-of-range faces of connected_components, 8 for the components a
 
 Command line: python -m dgmesh_amd.mesh_topology mesh.ply [...] prints one JSON report per file."""
 import argparse
-import ctypes
 import json
 
 import torch
@@ -29,14 +28,6 @@ from . import _lib
 
 INFO_FIELDS = ("edges", "boundary_edges", "nonmanifold_edges", "misoriented_edges", "regular_edges", "verts_used", "faces_valid",
                "adjacency")
-
-
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else ctypes.c_void_p(0)
-
-
-def _scratch(nbytes, dev):
-    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
 
 
 def _faces(name, faces, num_verts):
@@ -63,12 +54,12 @@ class EdgeTable:
         nbytes = L.dgm_mesh_edges_scratch_bytes(V, F)
         if nbytes == 0:
             raise ValueError(f"mesh_topology.{name}: a mesh of {V} vertices and {F} faces is over the supported 2^28 faces")
-        self.scratch = _scratch(nbytes, dev)
+        self.scratch = _lib.scratch(nbytes, dev)
         self.adj_offset = torch.empty(V + 1, dtype=torch.int32, device=dev)
         self.vert_flag = torch.empty(V, dtype=torch.uint8, device=dev)
         info = torch.empty(len(INFO_FIELDS), dtype=torch.int32, device=dev)
         with _lib.device_guard(dev):
-            _lib.check(L.dgm_mesh_edges_count(V, F, _vp(faces), _vp(self.scratch), _vp(self.adj_offset), _vp(self.vert_flag), _vp(info),
+            _lib.check(L.dgm_mesh_edges_count(V, F, _lib.vp(faces), _lib.vp(self.scratch), _lib.vp(self.adj_offset), _lib.vp(self.vert_flag), _lib.vp(info),
                                               _lib.stream_ptr()))
             self.info = dict(zip(INFO_FIELDS, info.tolist()))  # the one host synchronisation: the sizes
         self.E = self.info["edges"]
@@ -80,8 +71,8 @@ class EdgeTable:
         out = {"edges": new(edges, E, 2), "edge_faces": new(faces, E, 2), "edge_count": new(faces, E, 2), "adj": new(adjacency, 2 * E),
                "adj_kind": new(kind, 2 * E, dtype=torch.uint8)}
         with _lib.device_guard(dev):
-            _lib.check(self.L.dgm_mesh_edges_emit(self.V, self.F, _vp(self.scratch), E, _vp(self.adj_offset), _vp(out["adj"]),
-                                                  _vp(out["adj_kind"]), _vp(out["edges"]), _vp(out["edge_faces"]), _vp(out["edge_count"]),
+            _lib.check(self.L.dgm_mesh_edges_emit(self.V, self.F, _lib.vp(self.scratch), E, _lib.vp(self.adj_offset), _lib.vp(out["adj"]),
+                                                  _lib.vp(out["adj_kind"]), _lib.vp(out["edges"]), _lib.vp(out["edge_faces"]), _lib.vp(out["edge_count"]),
                                                   _lib.stream_ptr()))
         return out
 

@@ -21,17 +21,12 @@ Deviations from the reference: the sampling stream is th
 sampled; an empty surface raises instead of indexing an empty array (one without area raises one call later, AreaCheck); with several ranks rank 0's result is broadcast (trainer.py).
 No CPU fallback: every function raises on CPU tensors.
 """
-import ctypes
 import os
 
 import torch
 
 from . import _lib
 from . import anchor as _A
-
-
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else None
 
 
 def _need_cuda(name, *ts):
@@ -63,7 +58,7 @@ def bbox(xyz, d_xyz=None, out=None, scratch=None):
     if scratch is None:
         scratch = bbox_scratch(x.device)
     with _lib.device_guard(x.device):
-        _lib.check(_lib.lib().dgm_ninit_bbox(x.shape[0], _vp(x), _vp(d), _vp(scratch), _vp(out), _lib.stream_ptr()))
+        _lib.check(_lib.lib().dgm_ninit_bbox(x.shape[0], _lib.vp(x), _lib.vp(d), _lib.vp(scratch), _lib.vp(out), _lib.stream_ptr()))
     return out
 
 
@@ -109,7 +104,7 @@ def face_areas(verts, faces):
     f = faces.detach().contiguous().to(torch.int32)
     area = torch.empty(f.shape[0], dtype=torch.float32, device=v.device)
     with _lib.device_guard(v.device):
-        _lib.check(_lib.lib().dgm_ninit_face_areas(v.shape[0], f.shape[0], _vp(v), _vp(f), _vp(area), _lib.stream_ptr()))
+        _lib.check(_lib.lib().dgm_ninit_face_areas(v.shape[0], f.shape[0], _lib.vp(v), _lib.vp(f), _lib.vp(area), _lib.stream_ptr()))
     return area
 
 
@@ -122,7 +117,7 @@ def cumulative_areas(area):
     cum = torch.empty(F, dtype=torch.float64, device=a.device)
     scratch = torch.empty(int(L.dgm_ninit_scan_scratch_bytes(F)), dtype=torch.uint8, device=a.device)
     with _lib.device_guard(a.device):
-        _lib.check(L.dgm_ninit_area_scan(F, _vp(a), _vp(scratch), _vp(cum), _lib.stream_ptr()))
+        _lib.check(L.dgm_ninit_area_scan(F, _lib.vp(a), _lib.vp(scratch), _lib.vp(cum), _lib.stream_ptr()))
     return cum
 
 
@@ -174,7 +169,7 @@ def _sample(verts, faces, count, generator, draws, check):
     points = torch.empty((count, 3), dtype=torch.float32, device=v.device)
     face_index = torch.empty(count, dtype=torch.int32, device=v.device)
     with _lib.device_guard(v.device):
-        _lib.check(_lib.lib().dgm_ninit_sample(V, F, count, _vp(v), _vp(f), _vp(cum), _vp(u), _vp(points), _vp(face_index),
+        _lib.check(_lib.lib().dgm_ninit_sample(V, F, count, _lib.vp(v), _lib.vp(f), _lib.vp(cum), _lib.vp(u), _lib.vp(points), _lib.vp(face_index),
                                                _lib.stream_ptr()))
     return points, face_index, cum[-1:]
 

@@ -38,7 +38,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .mesh_raster import _check_rast, _need, _st, _vp, clip_positions, rasterize, render_mesh
+from .mesh_raster import _check_rast, _need, _st, clip_positions, rasterize, render_mesh
 
 MATERIAL = {"ambient": 0.5, "diffuse": 0.3, "specular": 0.2 * 0.2, "shininess": 10.0, "base_color": (1.0, 1.0, 1.0)}
 MAX_PANELS = 4
@@ -71,7 +71,7 @@ def vertex_normals(verts, faces):
     V, F = int(verts.shape[0]), int(faces.shape[0])
     normals = torch.empty_like(verts)
     with _lib.device_guard(verts.device):
-        _lib.check(_lib.lib().dgm_vertex_normals(V, F, _vp(verts), _vp(faces), _vp(normals), _st()))
+        _lib.check(_lib.lib().dgm_vertex_normals(V, F, _lib.vp(verts), _lib.vp(faces), _lib.vp(normals), _st()))
     return normals
 
 
@@ -113,7 +113,7 @@ def mesh_shape_renderer(verts, faces, cam, *, light_dir=None, rast=None, backgro
     normals = vertex_normals(verts, faces)
     image = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
     with _lib.device_guard(dev):
-        _lib.check(_lib.lib().dgm_mesh_shade(V, F, H, W, _vp(verts), _vp(normals), _vp(faces), _vp(rast), _vp(params), _vp(image), _st()))
+        _lib.check(_lib.lib().dgm_mesh_shade(V, F, H, W, _lib.vp(verts), _lib.vp(normals), _lib.vp(faces), _lib.vp(rast), _lib.vp(params), _lib.vp(image), _st()))
     return image
 
 
@@ -142,7 +142,7 @@ def splat_points(pos_clip, H, W, colors=None, color=(0.0, 0.0, 1.0), size=1, bac
     scratch = torch.empty(int(L.dgm_point_splat_scratch_bytes(H, W)), dtype=torch.uint8, device=dev)
     image = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
     with _lib.device_guard(dev):
-        _lib.check(L.dgm_point_splat(N, H, W, _vp(pos_clip), _vp(colors), size, bg6, _vp(scratch), _vp(image), _st()))
+        _lib.check(L.dgm_point_splat(N, H, W, _lib.vp(pos_clip), _lib.vp(colors), size, bg6, _lib.vp(scratch), _lib.vp(image), _st()))
     if not return_ids:
         return image
     keys = scratch[:H * W * 8].view(torch.int64).reshape(H, W)  # (ordered z/w bits) << 32 | id; all ones: empty
@@ -218,7 +218,7 @@ def compose_frame(panels, downsample=1, out=None, layouts=None):
     ptrs = (ctypes.c_void_p * len(panels))(*[i[3].data_ptr() for i in info])
     lay = (ctypes.c_int * len(panels))(*[i[2] for i in info])
     with _lib.device_guard(dev):
-        _lib.check(_lib.lib().dgm_compose_frame(len(panels), ptrs, lay, H, W, d, _vp(out), _st()))
+        _lib.check(_lib.lib().dgm_compose_frame(len(panels), ptrs, lay, H, W, d, _lib.vp(out), _st()))
     return out
 
 

@@ -76,7 +76,7 @@ def main():
         L = lib.lib()
         scratch = torch.empty(int(L.dgm_wind_scratch_bytes(N, F)), dtype=torch.uint8, device=dev)
         out = torch.empty(N, dtype=torch.float32, device=dev)
-        vp = M._vp
+        vp = M._lib.vp
         raw = lambda: lib.check(L.dgm_wind_number(N, V, F, vp(points), vp(verts), vp(faces), vp(scratch), vp(out), lib.stream_ptr()))
         res["dgm_wind_number_ms"], _ = _times(raw, args.iters)
         res["raw_equals_wrapper"] = bool(torch.equal(out, w))

@@ -55,7 +55,7 @@ def main():
         h = M.grid_cell(p.box, args.grid)
         s, L, st = p.best, p.L, M._lib.stream_ptr
         box = torch.empty(6, dtype=torch.float32, device=dev)
-        vp, chk = M._vp, M._lib.check
+        vp, chk = M._lib.vp, M._lib.check
         p.count(h)
         g = p._grid_args(s)
         placed = torch.empty((V, 3), dtype=torch.float32, device=dev)

@@ -105,7 +105,7 @@ def main():
         E = table.E
         res.update(E=E, info=table.info)
         res["edge_table_ms"], res["edge_table_wall_ms"] = _times(whole_table, args.iters)
-        L, vp, chk, st = table.L, T._vp, T._lib.check, T._lib.stream_ptr
+        L, vp, chk, st = table.L, T._lib.vp, T._lib.check, T._lib.stream_ptr
         info = torch.empty(8, dtype=torch.int32, device=dev)
         res["count_ms"], _ = _times(lambda: chk(L.dgm_mesh_edges_count(V, F, vp(faces), vp(table.scratch), vp(table.adj_offset),
                                                                          vp(table.vert_flag), vp(info), st())), args.iters)
