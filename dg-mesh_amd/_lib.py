@@ -156,6 +156,11 @@ SYMBOLS = {
     "dgm_mesh_edges_count": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dgm_mesh_edges_emit": (_i, [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dgm_mesh_smooth_step": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _c.c_double, _i, _vp, _vp]),
+    "dgm_mesh_orient_scratch_bytes": (_c.c_size_t, [_i, _i]),
+    "dgm_mesh_orient": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "dgm_mesh_fill_scratch_bytes": (_c.c_size_t, [_i, _i]),
+    "dgm_mesh_fill_count": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "dgm_mesh_fill_emit": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "dgm_wind_scratch_bytes": (_c.c_size_t, [_i, _i]),
     "dgm_wind_number": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dgm_ray_accel_bytes": (_c.c_size_t, [_i]),

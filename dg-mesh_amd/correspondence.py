@@ -300,15 +300,16 @@ def render_correspondence(gaussians, deform, deform_back, template_cam, *, mesh,
 
 @torch.no_grad()
 def export_correspondence(gaussians, deform, deform_back, mesh, out_dir, frames=200, deform_normal=None, clean=None, simplify=None,
-                          smooth=None, *, t_ref=0.0, mode="reference", palette="checker", max_dist=None, n_tracks=2048, seed=0, cells=8):
+                          smooth=None, repair=None, *, t_ref=0.0, mode="reference", palette="checker", max_dist=None, n_tracks=2048, seed=0, cells=8):
     """visualize.export_dynamic_mesh's sequence (t = i / frames) with the correspondence on it, under out_dir/correspondence:
     frame_{i}.ply -- the mesh of frame i in its correspondence colours (ply_io.write_mesh_ply) --, tracks.npz -- tracks
     (T, K, 3) float32 with NaN where unmatched, found (T, K) bool, times (T,) -- and report.json (module docstring).  clean: as
     export_dynamic_mesh, applied to the WRITTEN meshes only (the colours follow their vertices); the snap and the tracks use the
     full meshes.  simplify: as export_dynamic_mesh, after `clean`, on the WRITTEN meshes only; a new vertex takes the colour of its
-    cluster's representative.  smooth: as export_dynamic_mesh, on the WRITTEN meshes only, after `clean` and BEFORE `simplify`.
+    cluster's representative.  smooth: as export_dynamic_mesh, on the WRITTEN meshes only, after `clean` and BEFORE `simplify`.  repair: as
+    export_dynamic_mesh, on the WRITTEN meshes only, LAST, after `simplify`; a new vertex takes the mean colour of its rim.
     -> {"paths": [...], "tracks_path", "report_path", "report", "tracks", "found", "times"}."""
-    from . import mesh_clean, mesh_simplify, mesh_smooth
+    from . import mesh_clean, mesh_repair, mesh_simplify, mesh_smooth
     from .ply_io import write_mesh_ply
     who = "export_correspondence"
     _check_options(who, mode, palette, n_tracks, cells)
@@ -328,6 +329,7 @@ def export_correspondence(gaussians, deform, deform_back, mesh, out_dir, frames=
         verts, faces, corr_color = mesh_clean.apply(clean, verts, faces, corr_color)
         verts, faces, corr_color = mesh_smooth.apply(smooth, verts, faces, corr_color)
         verts, faces, corr_color = mesh_simplify.apply(simplify, verts, faces, corr_color)
+        verts, faces, corr_color = mesh_repair.apply(repair, verts, faces, corr_color)
         paths.append(os.path.join(out_dir, "correspondence", f"frame_{i}.ply"))
         write_mesh_ply(paths[-1], verts, faces, vertex_colors=corr_color)
     times = np.arange(n, dtype=np.float32) / np.float32(n)

@@ -32,6 +32,7 @@
 
 #include "dgm_host.hpp"
 #include "mesh_scan.hpp"
+#include "mesh_unionfind.hpp"  // ld_parent, find_root, unite (shared with mesh_repair.hip)
 
 #pragma clang fp contract(off)
 
@@ -47,10 +48,6 @@ constexpr int SEL_MAX_BLOCKS = 1024;
 
 int tiles(long long n) { return (int)((n + MC_TILE - 1) / MC_TILE); }
 
-
-#define AGENT __HIP_MEMORY_SCOPE_AGENT
-
-__device__ __forceinline__ int ld_parent(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, AGENT); }
 
 // order-preserving float <-> unsigned (-NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN: a NaN orders by its bits)
 __device__ __forceinline__ unsigned f2key(float f) {
@@ -70,32 +67,7 @@ __global__ void __launch_bounds__(MC_THREADS) cc_init_kernel(int V, int* __restr
     if (v < V) parent[v] = (int)v;
 }
 
-// The root of v's tree, halving the path on the way (parent[v] = min(parent[v], grandparent)).
-__device__ __forceinline__ int find_root(int* parent, int v) {
-    int p = ld_parent(parent + v);
-    // ends: p = parent[v] < v strictly on every step that does not return (parent[x] <= x always), so v descends towards 0
-    while (p != v) {
-        const int g = ld_parent(parent + p);
-        if (g != p) __hip_atomic_fetch_min(parent + v, g, __ATOMIC_RELAXED, AGENT);
-        v = p;
-        p = g;
-    }
-    return v;
-}
-
-__device__ __forceinline__ void unite(int* parent, int a, int b) {
-    int ra = find_root(parent, a), rb = find_root(parent, b);
-    // ends: ra + rb decreases strictly on every pass that does not break: a failed CAS returned old < hi, and the root found from
-    // old is <= old.  A CAS fails only because another thread has made progress (it lowered parent[hi]): lock-free, nothing waits.
-    while (ra != rb) {
-        const int hi = ra > rb ? ra : rb, lo = ra > rb ? rb : ra;
-        int expected = hi;
-        if (__hip_atomic_compare_exchange_strong(parent + hi, &expected, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, AGENT)) break;
-        ra = find_root(parent, expected);  // (expected now holds parent[hi] < hi)
-        rb = lo;
-        rb = find_root(parent, rb);
-    }
-}
+// (find_root and unite: mesh_unionfind.hpp)
 
 // info[0]: faces with an index outside [0, V); info[1]: faces with all indices in range and two of them equal
 __global__ void __launch_bounds__(MC_THREADS) cc_hook_kernel(int V, int F, const int* __restrict__ faces, int* parent, int* info) {

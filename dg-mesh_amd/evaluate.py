@@ -86,7 +86,8 @@ def _mesh_view(mesh, gaussians, deform_back, d_xyz, d_normal, cam, white_backgro
 
 @torch.no_grad()
 def testing(gaussians, deform, deform_back, cameras, *, pipe, background, mesh=None, deform_normal=None, is_6dof=False,
-            white_background=True, out_dir=None, save_meshes=False, lpips=None, clean=None, simplify=None, smooth=None, save_glb=False):
+            white_background=True, out_dir=None, save_meshes=False, lpips=None, clean=None, simplify=None, smooth=None, repair=None,
+            save_glb=False):
     """testing() of R/train.py:559-761 without the image files.  Per camera: deform.step at the camera's
     fid, scene.render clamped to [0, 1]; with `mesh` (a trainer.MeshPhase that has a DPSR module) also mesh.psr -> mesh.surface ->
     deform_back + mesh.appearance on the vertices -> mesh_raster.render_mesh (deform_normal: the network whose first output is added
@@ -105,7 +106,9 @@ def testing(gaussians, deform, deform_back, cameras, *, pipe, background, mesh=N
     mesh_simplify.SimplifySpec (or a dict of its fields): the WRITTEN mesh only is decimated by quadric vertex clustering, after
     `clean`, the colours taken at the representatives.  smooth: None, or a mesh_smooth.SmoothSpec (or a dict of its fields): the
     WRITTEN mesh only is smoothed (mesh_smooth.smooth_mesh), after `clean` and BEFORE `simplify` -- denoised first, decimated after.
-    save_glb: also writes the reference's test_results/dynamic_glb/frame_{idx}.glb (R/train.py:740), the same written mesh with its
+    repair: None, or a mesh_repair.RepairSpec (or a dict of its fields): the WRITTEN mesh only is repaired (mesh_repair.repair_mesh:
+    every body oriented consistently and outwards, small holes filled) LAST, after `simplify`; a new vertex takes the mean colour of
+    its rim.  save_glb: also writes the reference's test_results/dynamic_glb/frame_{idx}.glb (R/train.py:740), the same written mesh with its
     vertex colours as binary glTF (glb_io.write_mesh_glb); needs mesh and out_dir.
 
     lpips: None, or {"alex": lpips.LPIPS, "vgg": lpips.LPIPS} with either key optional.  Each network then scores both images of a
@@ -159,10 +162,11 @@ def testing(gaussians, deform, deform_back, cameras, *, pipe, background, mesh=N
         for j, net in enumerate(nets):
             lpips[net]._into(*LP._checked(images, gt, net), lp_table[idx, j, :images.shape[0]])
         if save_meshes or save_glb:
-            from . import mesh_clean, mesh_simplify, mesh_smooth
+            from . import mesh_clean, mesh_repair, mesh_simplify, mesh_smooth
             w_verts, w_faces, w_color = mesh_clean.apply(clean, verts, faces, vtx_color)
             w_verts, w_faces, w_color = mesh_smooth.apply(smooth, w_verts, w_faces, w_color)
             w_verts, w_faces, w_color = mesh_simplify.apply(simplify, w_verts, w_faces, w_color)
+            w_verts, w_faces, w_color = mesh_repair.apply(repair, w_verts, w_faces, w_color)
             if save_meshes:
                 from .ply_io import write_mesh_ply
                 write_mesh_ply(os.path.join(saving_path, "dynamic_mesh", f"frame_{idx}.ply"), w_verts, w_faces, vertex_colors=w_color)

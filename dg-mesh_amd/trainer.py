@@ -224,14 +224,16 @@ class MeshPhase:
         return verts * g.gaussian_scale + g.gaussian_center, faces
 
     @torch.no_grad()
-    def extract_mesh(self, g, deform=None, deform_normal=None, t=None, clean=None, simplify=None, smooth=None):
+    def extract_mesh(self, g, deform=None, deform_normal=None, t=None, clean=None, simplify=None, smooth=None, repair=None):
         """export_mesh (R/scene/gaussian_model_dpsr_dynamic_anchor.py:831-856): world-space (verts, faces) of the surface at time t.
         deform / deform_normal: DeformModel-like objects with .step(xyz, t) (the first output is used), or None for the canonical
         Gaussians; t: a scalar time (float or tensor).  clean: None, or a mesh_clean.CleanSpec (or a dict of its fields): the
         components that fail it are removed (mesh_clean.clean_mesh).  simplify: None, or a mesh_simplify.SimplifySpec (or a dict of its
         fields): the mesh is then decimated by quadric vertex clustering (mesh_simplify.simplify_mesh), after `clean`.  smooth: None, or a
         mesh_smooth.SmoothSpec (or a dict of its fields): the mesh is smoothed (mesh_smooth.smooth_mesh) after `clean` and BEFORE
-        `simplify` -- denoised first, decimated after.  Write the result with ply_io.write_mesh_ply."""
+        `simplify` -- denoised first, decimated after.  repair: None, or a mesh_repair.RepairSpec (or a dict of its fields): the mesh
+        is repaired (mesh_repair.repair_mesh: every body oriented consistently and outwards, small holes filled) LAST, after `simplify`.
+        Never applied inside the training step.  Write the result with ply_io.write_mesh_ply."""
         if self.dpsr is None:
             raise RuntimeError("MeshPhase.extract_mesh needs the DPSR module")
         xyz = g.get_xyz
@@ -250,6 +252,9 @@ class MeshPhase:
         if simplify is not None:
             from . import mesh_simplify
             verts, faces = mesh_simplify.apply(simplify, verts, faces)
+        if repair is not None:
+            from . import mesh_repair
+            verts, faces = mesh_repair.apply(repair, verts, faces)
         return verts, faces
 
 

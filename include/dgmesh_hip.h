@@ -853,6 +853,53 @@ int dgm_mesh_edges_emit(int V, int F, char* scratch, int E, const int* adj_offse
 int dgm_mesh_smooth_step(int V, int A, const float* verts_in, const int* adj_offset, const int* adj, const unsigned char* adj_kind,
                          const unsigned char* vert_flag, double factor, int boundary, float* verts_out, void* stream);
 
+/* ---- mesh repair: a consistent, outward orientation per body and hole filling (csrc/mesh_repair.hip) ------------------------------------
+ * The last stage of the reference's mesh clean-up (pymeshlab meshing_close_holes, trimesh fill_holes, fix_inversion, fix_normals;
+ * dgmesh/scene/gaussian_model.py:652-691).  verts (V, 3) fp32, faces (F, 3) int32; every buffer is device memory, nothing is allocated
+ * and nothing is read back.  Both parts read the sorted lists that dgm_mesh_edges_count(V, F, faces, edges_scratch, ...) left in
+ * edges_scratch, for the SAME V, F and faces.  VALID faces, half-edges and edge classes are those of the edge table above; an
+ * invalid face is passed through and never flipped.  Everything is decided by integers: bit-reproducible.  F <= 2^28.
+ *   ADJACENT: two valid faces that share an edge which exactly two valid faces traverse; with counts (1, 1) they AGREE, with (2, 0)
+ *       or (0, 2) they DISAGREE.  Boundary and non-manifold edges connect nothing.  COMPONENTS are those of this adjacency; the
+ *       label of a component is its smallest face.  A component is ORIENTABLE when flips can make every connecting edge agree, CLOSED
+ *       when every half-edge of its faces lies on a connecting edge.
+ *   ORIENTATION: a non-orientable component is left as it is.  An orientable one has two consistent orientations, K (keeps its
+ *       smallest face) and the opposite.  The OPEN RULE takes the one that flips fewer faces, K on a tie.  With `outward`, a closed
+ *       component whose signed volume sum in orientation K is not 0 takes K when the sum is positive and the opposite when negative
+ *       (counted in "components inverted"); every other component takes the open rule.  Nested inner shells are turned outward too.
+ *       A flipped face (a, b, c) becomes (a, c, b).
+ *   SIGNED VOLUME: lo, hi = the fp32 box of the used vertices, e = the smallest integer with 2^e >= the longest side (fp64 hi - lo);
+ *       per face in orientation K, p, q, r = the fp64 corners minus fp64 lo,
+ *       det = px (qy rz - qz ry) - py (qx rz - qz rx) + pz (qx ry - qy rx) in that order without contraction, term = llrint(det
+ *       2^(30 - 3 e)) (round half even; |term| <= 6 2^30), 0 for a non-finite det; the component's sum is int64 (< 2^61).  A box that
+ *       is not finite or has no extent (or no used vertex) skips the volume rule for the whole mesh: "outward skipped" = 1.
+ *   dgm_mesh_orient: faces_out (F, 3) (not `faces` itself), flipped (F) bytes, info (8 ints) = components, closed components,
+ *       unorientable components, faces flipped, components inverted, outward skipped, 0, 0.  scratch:
+ *       dgm_mesh_orient_scratch_bytes(V, F) bytes (0 for a negative or unsupported size).
+ *   BOUNDARY HALF-EDGE: the directed side a->b that the single valid face of a boundary edge traverses -- reversed where `flipped`
+ *       (NULL: nothing is) marks that face, so the table of the unflipped faces serves the oriented mesh.  Its index is the rank of
+ *       its edge among the boundary edges in the edge table's order; B = info[1] of dgm_mesh_edges_count.  A vertex is SIMPLE when
+ *       exactly one boundary half-edge leaves it and exactly one arrives; next(a->b) = the boundary half-edge leaving b when b is
+ *       simple.  A HOLE is a closed cycle of next of n <= max_hole_edges half-edges (always n >= 3); its LEADER is its smallest
+ *       half-edge.  Longer cycles are counted ("holes too long"), as are the half-edges of chains that end at a vertex that is not
+ *       simple ("edges on open chains"); both are left open.
+ *   FILL: n == 3: one face (b, a, c') from the leader a->b and c' the head of its next.  n >= 4: one new vertex, (float)((the sum of
+ *       the rim vertices in fp64 from 0, in loop order from the leader's tail) / (double)n), and one face (b, a, new vertex) per
+ *       half-edge a->b.  New vertices follow the V given ones in leader order, new faces follow the F given ones in half-edge order.
+ *   dgm_mesh_fill_count: info (8 ints) = boundary edges, holes filled, holes too long, edges on open chains, vertices added, faces
+ *       added, 0, 0; the caller reads it back to size the outputs.  scratch: dgm_mesh_fill_scratch_bytes(V, B) bytes, handed on to
+ *       the emit call unchanged.
+ *   dgm_mesh_fill_emit: verts_out (V + nv, 3) and faces_out (F + nf, 3) = the given rows (`faces` may be the oriented faces), then
+ *       the new ones; nothing is written at or behind V + nv and F + nf rows. */
+size_t dgm_mesh_orient_scratch_bytes(int V, int F);
+int dgm_mesh_orient(int V, int F, const float* verts, const int* faces, char* edges_scratch, char* scratch, int outward, int* faces_out,
+                    unsigned char* flipped, int* info, void* stream);
+size_t dgm_mesh_fill_scratch_bytes(int V, int B);
+int dgm_mesh_fill_count(int V, int F, int B, const float* verts, char* edges_scratch, const unsigned char* flipped, int max_hole_edges,
+                        char* scratch, int* info, void* stream);
+int dgm_mesh_fill_emit(int V, int F, int B, const float* verts, const int* faces, char* scratch, int nv, int nf, float* verts_out,
+                       int* faces_out, void* stream);
+
 /* ---- inside / outside: the generalised winding number of query points (csrc/mesh_inside.hip) ------------------------------------------
  * What answers whether a point is inside a mesh (mesh_inside.py: contains, signed_distance, occupancy_grid, volume_iou).  points
  * (N, 3), verts (V, 3) fp32, faces (F, 3) int32; every buffer is device memory, nothing is allocated and nothing is read back.
