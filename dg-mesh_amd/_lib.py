@@ -180,6 +180,7 @@ SYMBOLS = {
     "dgm_resample": (_i, [_i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dgm_resample_nearest": (_i, [_i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "dgm_mlp_set_gemm": (_i, [_i]),
+    "dgm_mlp_set_reduce_in_pair": (_i, [_i]),
     "dgm_timenet_forward": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "dgm_timenet_backward": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dgm_mlp_workspace_bytes": (_c.c_size_t, [_i]),

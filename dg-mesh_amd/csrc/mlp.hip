@@ -322,17 +322,9 @@ __global__ void mlp_reduce_dw_kernel(int chunks, int db_chunks, int Kp, int in_f
 }
 
 // The same reduction in ONE pass for the matrix-core paths (256 partial tiles of 256 KB per layer: the read is the cost).
-struct ReduceDwJob {
-    int chunks, db_rows, Kp, in_features, nblocks;
-    int emb_rows, k_valid;  // Kp != 256 jobs: rows [0, emb_rows) are the embedding's (the first k_valid of them real columns), the rest the trunk's
-    int dst_off;  // Kp == 256 jobs: first input feature the rows go to (the skip layer's trunk rows as a job of their own)
-    const float* partial;
-    const float* partial_db;
-    float* dW;
-    float* db;
-};
+// (ReduceDwJob and the body of one piece, reduce_dw_piece, live in mlp_planes.hpp: the grouped paired launches run pieces too)
 struct ReduceDwBatch {
-    int emb_dim, n_jobs;
+    int n_jobs;
     ReduceDwJob job[18];  // (nine per network: a grouped backward pass reduces two networks in one launch)
     // blockIdx.y >= n_jobs: the heads' partial sums (mlp_heads_bwd_kernel) ride along, see reduce_heads_body; one set per network
     struct Heads {
@@ -347,25 +339,17 @@ __device__ __forceinline__ void reduce_heads_body(int bx, int o, int chunks, int
                                                   const float* __restrict__ partial_b, float* __restrict__ dWh,
                                                   float* __restrict__ dbh);
 // All eight layers of a network in ONE launch at the end of its backward pass (blockIdx.y = layer; every layer keeps its own
-// partial tiles until then).  Workgroup = a KT x JT piece of the (k, j) plane as 64 float4 positions (one wave-wide load =
-// KT row segments of JT * 4 contiguous bytes of one partial tile), times four groups of chunks (the four waves): every
-// thread streams its group's chunks with sixteen 16-byte loads in flight, the four group sums meet in LDS (fixed order), and
-// the piece is written transposed into the PyTorch (out, in) layout.  With eight layers in the grid there are enough
-// workgroups (>= 2048) to read in segments of 256+ bytes and still fill the chip, which a single layer's launch could not.
-// The first 32 workgroups of a layer also reduce eight columns each of its bias-gradient rows (db_rows of them).
+// partial tiles until then).  Workgroup = one piece of a job (reduce_dw_piece, mlp_planes.hpp).  With eight layers in the grid there
+// are enough workgroups (>= 2048) to read in segments of 256+ bytes and still fill the chip, which a single layer's launch could not.
+// A grouped pass hands the first pieces of its hidden layers' jobs to the paired launches (ReduceDwJob::first_block); this launch
+// does the rest, in the same job order.
 // (round 4, measured at N = 100 k: 86-88 us whatever the piece shape -- RDW_KT = 1, 2, 4, 8, i.e. segments of 1 KB .. 128 B --
 // and whatever the distance between consecutive chunks' tiles -- 256 KB, or padded by 256 B / 4 KB / 8.25 KB against channel
 // aliasing: 323 MB of L2 misses at 3.7 TB/s is what a read of tiles the previous launches just wrote gets here)
-#ifndef RDW_KT
-#define RDW_KT 4
-#endif
-static constexpr int RDW_JT = 256 / RDW_KT;  // KT * JT = 256 elements per workgroup
 static inline int reduce_dw_blocks(int Kp) { return (Kp / RDW_KT) * (MLP_W / RDW_JT); }
 __global__ void __launch_bounds__(256)
 mlp_reduce_dw_all_kernel(const ReduceDwBatch rb) {
-    constexpr int KT = RDW_KT, JT = RDW_JT, JQ = JT / 4, JB = MLP_W / JT;
-    __shared__ float4 red[4][64];
-    __shared__ float redb[32][8];
+    __shared__ __attribute__((aligned(16))) float red[RDW_LDS_FLOATS];
     if ((int)blockIdx.y >= rb.n_jobs) {  // (workgroup-uniform branch)
         const ReduceDwBatch::Heads& h = rb.heads[(int)blockIdx.y - rb.n_jobs];
         if ((int)blockIdx.x < 8 * h.nout)
@@ -373,66 +357,8 @@ mlp_reduce_dw_all_kernel(const ReduceDwBatch rb) {
         return;
     }
     const ReduceDwJob& jb = rb.job[blockIdx.y];
-    if ((int)blockIdx.x >= jb.nblocks) return;
-    const int chunks = jb.chunks, db_rows = jb.db_rows, Kp = jb.Kp, in_features = jb.in_features, emb_dim = rb.emb_dim;
-    const float* __restrict__ partial = jb.partial;
-    const float* __restrict__ partial_db = jb.partial_db;
-    float* __restrict__ dW = jb.dW;
-    float* __restrict__ db = jb.db;
-    const int tid = threadIdx.x, pos = tid & 63, grp = tid >> 6;
-    const int k0 = ((int)blockIdx.x / JB) * KT, j0 = ((int)blockIdx.x % JB) * JT;
-    {
-        const int k = k0 + pos / JQ, j = j0 + (pos % JQ) * 4;
-        const int per = (chunks + 3) >> 2;
-        const int c1 = min(chunks, (grp + 1) * per);
-        int c = grp * per;
-        const size_t cs = (size_t)Kp * MLP_W;
-        const float* src = partial + (size_t)k * MLP_W + j;
-        float4 sp[16];
-#pragma unroll
-        for (int u = 0; u < 16; u++) sp[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (; c + 16 <= c1; c += 16) {
-            float4 v[16];
-#pragma unroll
-            for (int u = 0; u < 16; u++) v[u] = *reinterpret_cast<const float4*>(src + (size_t)(c + u) * cs);
-#pragma unroll
-            for (int u = 0; u < 16; u++) sp[u].x += v[u].x, sp[u].y += v[u].y, sp[u].z += v[u].z, sp[u].w += v[u].w;
-        }
-        for (; c < c1; c++) {
-            const float4 v = *reinterpret_cast<const float4*>(src + (size_t)c * cs);
-            sp[0].x += v.x, sp[0].y += v.y, sp[0].z += v.z, sp[0].w += v.w;
-        }
-#pragma unroll
-        for (int u = 8; u >= 1; u >>= 1)
-#pragma unroll
-            for (int v = 0; v < u; v++)
-                sp[v].x += sp[v + u].x, sp[v].y += sp[v + u].y, sp[v].z += sp[v + u].z, sp[v].w += sp[v + u].w;
-        red[grp][pos] = sp[0];
-    }
-    const bool do_db = db != nullptr && blockIdx.x < 32;
-    if (do_db) {
-        const int col = blockIdx.x * 8 + (tid & 7), g32 = tid >> 3;
-        float s = 0.f;
-        for (int r = g32; r < db_rows; r += 32) s += partial_db[(size_t)r * MLP_W + col];
-        redb[g32][tid & 7] = s;
-    }
-    __syncthreads();
-    {   // thread -> row k0 + tid % KT, column j0 + tid / KT: consecutive threads write consecutive k of one output row
-        const int kk = tid % KT, jj = tid / KT;
-        const float* r = reinterpret_cast<const float*>(&red[0][0]) + (kk * JQ + (jj >> 2)) * 4 + (jj & 3);
-        const float s = ((r[0] + r[256]) + r[512]) + r[768];
-        const int k = k0 + kk;
-        int dst;
-        if (Kp == MLP_W) dst = k + jb.dst_off;
-        else if (k < jb.emb_rows) dst = k < jb.k_valid ? k : -1;
-        else dst = k - jb.emb_rows + emb_dim;
-        if (dst >= 0) dW[(size_t)(j0 + jj) * in_features + dst] = s;
-    }
-    if (do_db && tid < 8) {
-        float s = redb[0][tid];
-        for (int g = 1; g < 32; g++) s += redb[g][tid];
-        db[blockIdx.x * 8 + tid] = s;
-    }
+    if ((int)blockIdx.x < jb.first_block || (int)blockIdx.x >= jb.nblocks) return;
+    reduce_dw_piece<16>(jb, (int)blockIdx.x, (int)threadIdx.x, red);
 }
 
 // ---- small dense ops around the trunk ----------------------------------------------------------------------------------
@@ -726,6 +652,7 @@ struct Ws {
     uint4 *Wh4f, *Wh4b;
     float *wsc_hf, *wsc_hb;
     float *bias_s[8];           // round 6: biases times their layer's column scales (mlp_prep4c_kernel)
+    unsigned* tickets;          // eight counters: the reduce role of the grouped paired launches (pair_reduce_role), cleared by every grouped pass
     float *beff[2], *temb_row;  // round 6: the call's time row, kept for the backward pass (beff: the folded biases of the first version, unused -- they are formed where the biases are pre-scaled)
     size_t bytes;
 };
@@ -759,6 +686,19 @@ int g_gemm_mode = [] {
     if (strcmp(e, "f16x3p5") == 0) return 5;
     if (strcmp(e, "f16x3p") != 0) fprintf(stderr, "libdgmesh_hip: unknown DGM_MLP_GEMM=\"%s\" (f16x3p | f16x3p8 | f32): using f16x3p\n", e);
     return 3;
+}();
+// Pieces per K = 256 reduction job that a grouped backward pass reduces inside the NEXT layer's paired launch (pair_reduce_role,
+// mlp_planes.hpp) instead of in the final mlp_reduce_dw_all_kernel launch: 0 = none (the launches of before), values above a job's
+// piece count mean all of it.  dgm_mlp_set_reduce_in_pair() / DGM_MLP_REDUCE_IN_PAIR=<n>; the gradients do not depend on it.
+// Off by default: at the full cap the kernels of a step take 59 us less, but the bench's gain of 1.2-1.8 % is smaller
+// than its run-to-run spread on one box (profiles/reduce_in_pair_bench_ab.json), and a gain that cannot be told from noise is not one.
+#ifndef P4_REDUCE_IN_PAIR
+#define P4_REDUCE_IN_PAIR 0
+#endif
+int g_reduce_in_pair = [] {
+    const char* e = getenv("DGM_MLP_REDUCE_IN_PAIR");
+    const int n = e ? atoi(e) : P4_REDUCE_IN_PAIR;
+    return n < 0 ? 0 : n;
 }();
 // arithmetic the last forward pass on a workspace ran in: the backward pass must match (its scales and masks were produced by
 // that forward pass).  A small host-side table keyed by the workspace pointer; an unknown workspace is not checked.
@@ -849,6 +789,7 @@ Ws carve(char* base, int N) {
     w.beff[1] = take(MLP_W * 4);
     for (int l = 0; l < 8; l++) w.bias_s[l] = take(MLP_W * 4);
     w.temb_row = take(64 * 4);
+    w.tickets = (unsigned*)take(8 * 4);
     w.bytes = (size_t)(p - base) + 256;
     return w;
 }
@@ -1119,13 +1060,13 @@ int backward_planes(const dgm_mlp_params* p, int N, const float* dOut, int temb_
     }
     P4_LAUNCH((mlp_dw4_kernel<8, 1, 1024, 512, 128, 64>), CfgDwH::LDS, pl.chunks, st, d)
     ReduceDwBatch rb;
-    rb.emb_dim = p->emb_dim, rb.n_jobs = 0;
+    rb.n_jobs = 0;
     int rb_blocks = 0, n_pending = 0;
     auto add_job = [&](int slot, int chunks, int db_rows, int Kp, int in_features, int dst_off, const float* partial,
                        const float* partial_db, float* dWp, float* dbp) {
         ReduceDwJob& jb = rb.job[slot];
         jb.chunks = chunks, jb.db_rows = db_rows, jb.Kp = Kp, jb.in_features = in_features, jb.nblocks = reduce_dw_blocks(Kp);
-        jb.emb_rows = EW, jb.k_valid = fold ? MLP_XE : p->emb_dim;
+        jb.first_block = 0, jb.emb_rows = EW, jb.k_valid = fold ? MLP_XE : p->emb_dim, jb.emb_dim = p->emb_dim;
         jb.dst_off = dst_off, jb.partial = partial, jb.partial_db = partial_db, jb.dW = dWp, jb.db = dbp;
         if (jb.nblocks > rb_blocks) rb_blocks = jb.nblocks;
     };
@@ -1293,6 +1234,7 @@ int backward_planes_group(const GroupNet* nets, int N, const int n_wg, hipStream
         Dout4GroupArgs da;
         for (int i = 0; i < 2; i++)
             da.NC[i] = nets[i].p->n_out, da.dOut[i] = nets[i].dOut, da.Dp[i] = nets[i].w.Dp, da.Dexp[i] = nets[i].w.Dexp, da.partial_b[i] = nets[i].w.partial_hb;
+        da.tickets = nets[0].w.tickets;
         hipLaunchKernelGGL(mlp_dout4_group_kernel, dim3((nt + 3) / 4, 2), dim3(256), 0, st, N, nt, da);
     }
     unsigned char *G[2], *Gn[2];
@@ -1336,13 +1278,19 @@ int backward_planes_group(const GroupNet* nets, int N, const int n_wg, hipStream
     }
     ReduceDwBatch rb;
     memset(&rb, 0, sizeof(rb));
-    rb.emb_dim = nets[0].p->emb_dim;  // (the caller checked: the same for both networks)
     int rb_blocks = 0, n_pending = 0;
+    // Reduce role of the paired launches (pair_reduce_role, mlp_planes.hpp): the launch of layer l reduces the first n_hidden pieces
+    // of layer l + 1's K = 256 jobs, whose tiles the launch before it wrote.  Layer 7's launch has nothing to reduce yet, layer 1's
+    // jobs have no launch behind them: six of the seven layers can be hidden.
+    const int n_hidden = g_reduce_in_pair < reduce_dw_blocks(MLP_W) ? g_reduce_in_pair : reduce_dw_blocks(MLP_W);
+    PairReduceArgs pr;
+    memset(&pr, 0, sizeof(pr));
+    int hidden_slot[2] = {0, 0};  // rb.job slots of the K = 256 jobs the previous paired launch's tiles belong to
     auto add_job = [&](const dgm_mlp_params* p, int chunks, int db_rows, int Kp, int in_features, int dst_off, const float* partial,
                        const float* partial_db, float* dWp, float* dbp) {
         ReduceDwJob& jb = rb.job[n_pending++];
         jb.chunks = chunks, jb.db_rows = db_rows, jb.Kp = Kp, jb.in_features = in_features, jb.nblocks = reduce_dw_blocks(Kp);
-        jb.emb_rows = EW, jb.k_valid = MLP_XE;
+        jb.first_block = 0, jb.emb_rows = EW, jb.k_valid = MLP_XE, jb.emb_dim = nets[0].p->emb_dim;  // (the caller checked: the same for both networks)
         jb.dst_off = dst_off, jb.partial = partial, jb.partial_db = partial_db, jb.dW = dWp, jb.db = dbp;
         if (jb.nblocks > rb_blocks) rb_blocks = jb.nblocks;
     };
@@ -1377,13 +1325,24 @@ int backward_planes_group(const GroupNet* nets, int N, const int n_wg, hipStream
             else
                 add_job(nets[i].p, chunks_pair, 8 * chunks_pair, MLP_W, layer_in(nets[i].p, l), 0, d.partial, d.partial_db, nets[i].dW[l], nets[i].db[l]);
         }
+        // this launch's reduce role: the jobs the previous iteration queued (their tiles are complete); the final launch skips those pieces
+        pr.n_hidden = (l < 7 && n_hidden > 0) ? n_hidden : 0;
+        pr.ticket = nets[0].w.tickets + l;
+        if (pr.n_hidden > 0)
+            for (int i = 0; i < 2; i++) {
+                ReduceDwJob& jb = rb.job[hidden_slot[i]];
+                jb.first_block = pr.n_hidden;
+                pr.job[i] = jb;
+            }
+        for (int i = 0; i < 2; i++) hidden_slot[i] = n_pending - 2 + i;
         dgm::prof_begin(DGM_STAGE_MLP_BWD_PAIR, st, 2);  // (counts as the two layer passes it carries)
         {
             static bool done_[DGM_MAX_DEVICES] = {false};
             constexpr int LDS_PAIR = CfgBwdC::LDS > CfgDw::LDS ? CfgBwdC::LDS : CfgDw::LDS;
             if (p4_lds_attr(mlp_bwd_pair_group_kernel<true>, LDS_PAIR, &done_[current_device_slot()]) != hipSuccess)
                 return fail("mlp: cannot raise the LDS limit of mlp_bwd_pair_group_kernel");
-            hipLaunchKernelGGL(mlp_bwd_pair_group_kernel<true>, dim3(4 * n_wg), dim3(512), LDS_PAIR, st, pg, n_wg, cpw, n_dw);
+            static_assert(LDS_PAIR >= 2 * RDW_LDS_FLOATS * 4 + 16, "the reduce role's two pieces and its ticket slot live in the launch's LDS");
+            hipLaunchKernelGGL(mlp_bwd_pair_group_kernel<true>, dim3(4 * n_wg), dim3(512), LDS_PAIR, st, pg, n_wg, cpw, n_dw, pr);
         }
         dgm::prof_end(DGM_STAGE_MLP_BWD_PAIR, st);
         for (int i = 0; i < 2; i++) {
@@ -1426,6 +1385,12 @@ extern "C" {
 int dgm_mlp_set_gemm(int mode) {
     const int prev = g_gemm_mode;
     if (mode == 1 || mode == 3 || mode == 4 || mode == 5) g_gemm_mode = mode;  // (0, "bf16x6 for every GEMM", and 2, "f16x3" on fp32 rows, are retired: ignored)
+    return prev;
+}
+
+int dgm_mlp_set_reduce_in_pair(int pieces) {
+    const int prev = g_reduce_in_pair;
+    if (pieces >= 0) g_reduce_in_pair = pieces;
     return prev;
 }
 

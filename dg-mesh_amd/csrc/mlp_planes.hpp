@@ -1324,9 +1324,160 @@ struct PairGroupArgs {
     Gemm4Args ga[2];
     Dw4Args da[2];
 };
+
+// ---- one piece of the weight-gradient reduction (mlp_reduce_dw_all_kernel of mlp.hip, and the reduce role below) ---------------
+// A job sums the `chunks` partial tiles (Kp x 256 floats each) of one layer and network; a piece is KT x JT elements of the (k, j)
+// plane as 64 float4 positions (one wave-wide load = KT row segments of JT * 4 contiguous bytes of one partial tile), times four
+// groups of chunks (the four waves of the 256 threads): every thread streams its group's chunks with sixteen (or 32) 16-byte loads
+// in flight into sixteen running sums, folds them in a tree, the four group sums meet in LDS as ((g0 + g1) + g2) + g3, and the piece is
+// written transposed into the PyTorch (out, in) layout.  The first 32 pieces of a job also reduce eight columns each of its
+// bias-gradient rows.  Which chunk enters which running sum and the order of every add are fixed here and nowhere else: whoever
+// runs a piece -- a workgroup of the stand-alone launch or half a workgroup of a paired launch -- writes the same bits.
+#ifndef RDW_KT
+#define RDW_KT 4
+#endif
+static constexpr int RDW_JT = 256 / RDW_KT;  // KT * JT = 256 elements per piece
+static constexpr int RDW_LDS_FLOATS = 4 * 64 * 4 + 32 * 8;  // a piece's LDS: float4 red[4][64], float redb[32][8] (5 KB)
+struct ReduceDwJob {
+    int chunks, db_rows, Kp, in_features, nblocks;
+    int first_block;  // pieces [0, first_block) were reduced inside the next layer's paired launch (reduce role): the final launch skips them
+    int emb_rows, k_valid, emb_dim;  // Kp != 256 jobs: rows [0, emb_rows) are the embedding's (the first k_valid of them real columns), the rest the trunk's (from column emb_dim)
+    int dst_off;  // Kp == 256 jobs: first input feature the rows go to (the skip layer's trunk rows as a job of their own)
+    const float* partial;
+    const float* partial_db;
+    float* dW;
+    float* db;
+};
+// tid in [0, 256); lds: RDW_LDS_FLOATS floats, 16-byte aligned, this piece's own.  Contains ONE __syncthreads(): every thread of the
+// workgroup calls it the same number of times.
+template <int DEPTH>  // chunks whose loads a thread has in flight: 16 or 32
+__device__ __forceinline__ void reduce_dw_piece(const ReduceDwJob& jb, const int piece, const int tid, float* __restrict__ lds) {
+    constexpr int KT = RDW_KT, JT = RDW_JT, JQ = JT / 4, JB = 256 / JT;
+    float4* red = reinterpret_cast<float4*>(lds);  // [4][64]
+    float* redb = lds + 4 * 64 * 4;                 // [32][8]
+    const int chunks = jb.chunks, db_rows = jb.db_rows, Kp = jb.Kp, in_features = jb.in_features;
+    const float* __restrict__ partial = jb.partial;
+    const float* __restrict__ partial_db = jb.partial_db;
+    float* __restrict__ dW = jb.dW;
+    float* __restrict__ db = jb.db;
+    const int pos = tid & 63, grp = tid >> 6;
+    const int k0 = (piece / JB) * KT, j0 = (piece % JB) * JT;
+    {
+        const int k = k0 + pos / JQ, j = j0 + (pos % JQ) * 4;
+        const int per = (chunks + 3) >> 2;
+        const int c1 = min(chunks, (grp + 1) * per);
+        int c = grp * per;
+        const size_t cs = (size_t)Kp * 256;
+        const float* src = partial + (size_t)k * 256 + j;
+        float4 sp[16];
+#pragma unroll
+        for (int u = 0; u < 16; u++) sp[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (DEPTH == 32) {  // two rounds of sixteen chunks with all their loads in flight at once; the adds are those of two rounds
+            for (; c + 32 <= c1; c += 32) {
+                float4 v[32];
+#pragma unroll
+                for (int u = 0; u < 32; u++) v[u] = *reinterpret_cast<const float4*>(src + (size_t)(c + u) * cs);
+#pragma unroll
+                for (int u = 0; u < 32; u++) sp[u & 15].x += v[u].x, sp[u & 15].y += v[u].y, sp[u & 15].z += v[u].z, sp[u & 15].w += v[u].w;
+            }
+        }
+        for (; c + 16 <= c1; c += 16) {
+            float4 v[16];
+#pragma unroll
+            for (int u = 0; u < 16; u++) v[u] = *reinterpret_cast<const float4*>(src + (size_t)(c + u) * cs);
+#pragma unroll
+            for (int u = 0; u < 16; u++) sp[u].x += v[u].x, sp[u].y += v[u].y, sp[u].z += v[u].z, sp[u].w += v[u].w;
+        }
+        if (c < c1) {  // the last chunks (fewer than sixteen) go into sum 0 one after the other: loaded together, added in that order
+            float4 v[15];
+#pragma unroll
+            for (int u = 0; u < 15; u++)
+                if (c + u < c1) v[u] = *reinterpret_cast<const float4*>(src + (size_t)(c + u) * cs);  // (c1 is wave-uniform)
+#pragma unroll
+            for (int u = 0; u < 15; u++)
+                if (c + u < c1) sp[0].x += v[u].x, sp[0].y += v[u].y, sp[0].z += v[u].z, sp[0].w += v[u].w;
+        }
+#pragma unroll
+        for (int u = 8; u >= 1; u >>= 1)
+#pragma unroll
+            for (int v = 0; v < u; v++)
+                sp[v].x += sp[v + u].x, sp[v].y += sp[v + u].y, sp[v].z += sp[v + u].z, sp[v].w += sp[v + u].w;
+        red[grp * 64 + pos] = sp[0];
+    }
+    const bool do_db = db != nullptr && piece < 32;
+    if (do_db) {
+        const int col = piece * 8 + (tid & 7), g32 = tid >> 3;
+        float s = 0.f;
+        for (int r = g32; r < db_rows; r += 32 * 16) {  // one sum over the rows g32, g32 + 32, ... in that order, sixteen loads in flight
+            float v[16];
+#pragma unroll
+            for (int u = 0; u < 16; u++)
+                if (r + 32 * u < db_rows) v[u] = partial_db[(size_t)(r + 32 * u) * 256 + col];
+#pragma unroll
+            for (int u = 0; u < 16; u++)
+                if (r + 32 * u < db_rows) s += v[u];
+        }
+        redb[g32 * 8 + (tid & 7)] = s;
+    }
+    __syncthreads();
+    {   // thread -> row k0 + tid % KT, column j0 + tid / KT: consecutive threads write consecutive k of one output row
+        const int kk = tid % KT, jj = tid / KT;
+        const float* r = lds + (kk * JQ + (jj >> 2)) * 4 + (jj & 3);
+        const float s = ((r[0] + r[256]) + r[512]) + r[768];
+        const int k = k0 + kk;
+        int dst;
+        if (Kp == 256) dst = k + jb.dst_off;
+        else if (k < jb.emb_rows) dst = k < jb.k_valid ? k : -1;
+        else dst = k - jb.emb_rows + jb.emb_dim;
+        if (dst >= 0) dW[(size_t)(j0 + jj) * in_features + dst] = s;
+    }
+    if (do_db && tid < 8) {
+        float s = redb[tid];
+        for (int g = 1; g < 32; g++) s += redb[g * 8 + tid];
+        db[piece * 8 + tid] = s;
+    }
+}
+
+// ---- the reduce role of a grouped paired launch ----------------------------------------------------------------------------------
+// The partial tiles of layer l + 1 are complete when its paired launch has ended, and the paired launch of layer l is ordered behind
+// it on the stream: its workgroups can reduce them with no synchronisation inside a kernel.  Every workgroup first runs its own
+// share (weight-gradient chunks or GEMM tiles) and then takes tickets from one counter until the first n_hidden pieces of both
+// networks' jobs are handed out; ticket t is piece t of both jobs, one per 256-thread half of the workgroup on LDS of its own (the
+// pieces that also reduce bias rows come first and go to the workgroups without a share).  Workgroups
+// without a share (the last ones of either role when the chunks do not divide by the workgroups) start on tickets at once, the role
+// that ends first follows.  Nobody waits for anybody: a workgroup that finds the counter past the end returns.  The next ticket is
+// requested before the current pieces are read (a dependent round trip to the counter costs several us under load), so every
+// workgroup draws one ticket more than it serves and the counter ends at n_hidden + gridDim.x; the pass's first launch
+// (mlp_dout4_group_kernel) clears the counters, one per paired launch, in the workspace of the first network.
+struct PairReduceArgs {
+    ReduceDwJob job[2];  // the two networks' K = 256 jobs of the layer above
+    int n_hidden;        // pieces [0, n_hidden) of either job are reduced here; 0 = role off
+    unsigned* ticket;
+};
+__device__ __forceinline__ void pair_reduce_role(const PairReduceArgs& r, unsigned char* smem) {
+    const int tid = threadIdx.x;
+    const int half = __builtin_amdgcn_readfirstlane(tid >> 8);
+    float* lds = reinterpret_cast<float*>(smem) + half * RDW_LDS_FLOATS;
+    unsigned* slot = reinterpret_cast<unsigned*>(smem) + 2 * RDW_LDS_FLOATS;
+    const unsigned n_tickets = (unsigned)r.n_hidden;
+    __syncthreads();  // (the workgroup's own share is done with the LDS)
+    if (tid == 0) *slot = __hip_atomic_fetch_add(r.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    unsigned t = __builtin_amdgcn_readfirstlane(*slot);
+#pragma unroll 1
+    while (t < n_tickets) {  // (workgroup-uniform: the barriers match)
+        unsigned tn = 0;
+        if (tid == 0) tn = __hip_atomic_fetch_add(r.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        reduce_dw_piece<32>(r.job[half], (int)t, tid & 255, lds);
+        if (tid == 0) *slot = tn;  // (everyone read the slot before the piece's barrier)
+        __syncthreads();           // the ticket for all; the piece's LDS is free again
+        t = __builtin_amdgcn_readfirstlane(*slot);
+    }
+}
+
 template <bool COLSC>
 __global__ void __launch_bounds__(512)
-mlp_bwd_pair_group_kernel(const PairGroupArgs s, const int n_wg, const int cpw, const int n_chunks) {
+mlp_bwd_pair_group_kernel(const PairGroupArgs s, const int n_wg, const int cpw, const int n_chunks, const PairReduceArgs r) {
     extern __shared__ __attribute__((aligned(16))) unsigned char p4_smem[];
     const int net = __builtin_amdgcn_readfirstlane((int)blockIdx.x >= 2 * n_wg ? 1 : 0);
     const int w = (int)blockIdx.x - net * 2 * n_wg;
@@ -1345,6 +1496,7 @@ mlp_bwd_pair_group_kernel(const PairGroupArgs s, const int n_wg, const int cpw, 
         const int cnt = min(span, ga.ntiles - first);
         gemm4_body<16, 1024, 512, 1, false, 8, COLSC>(ga, first, 1, p4_smem, cnt > 0 ? cnt : 0);
     }
+    if (r.n_hidden > 0) pair_reduce_role(r, p4_smem);  // (a kernel argument: workgroup-uniform)
 }
 // The stand-alone launches of a backward pass for both networks: blockIdx.y = network.
 struct Dw4GroupArgs {
@@ -1373,10 +1525,12 @@ struct Dout4GroupArgs {
     unsigned char* Dp[2];
     int* Dexp[2];
     float* partial_b[2];
+    unsigned* tickets;  // the paired launches' ticket counters (pair_reduce_role), cleared here: the first launch of the pass
 };
 __global__ void __launch_bounds__(256)
 mlp_dout4_group_kernel(int N, int ntiles, const Dout4GroupArgs s) {
     const int i = blockIdx.y;
+    if (blockIdx.x == 0 && i == 0 && threadIdx.x < 8) s.tickets[threadIdx.x] = 0u;
     dout4_body(N, ntiles, s.NC[i], s.dOut[i], s.Dp[i], s.Dexp[i], s.partial_b[i]);
 }
 

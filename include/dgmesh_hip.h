@@ -71,7 +71,7 @@ extern "C" {
  *      dgm_image_composite_bytes / dgm_resample (resizing a dataset's images), dgm_lpips* (LPIPS of the test views),
  *      dgm_png_expand / dgm_image_ingest_masked / dgm_resample_nearest (real captures: mask PNGs and masked frames); dgm_png_unfilter
  *      also takes channels = 1; dgm_mesh_* (cleaning an extracted mesh); dgm_surf_* / dgm_corr_palette (mesh correspondence);
- *      dgm_ray_* (ray casting against a mesh). */
+ *      dgm_ray_* (ray casting against a mesh); dgm_mlp_set_reduce_in_pair. */
 #define DGM_ABI_VERSION 5
 
 /* Allocator callback: must return a device pointer to at least `bytes` bytes (128-byte aligned),
@@ -279,6 +279,13 @@ typedef struct {
  * retired in rounds 4 / 5 and are ignored.)  Returns the previous mode; any other value only queries.  Process-wide; the initial
  * value comes from the environment variable DGM_MLP_GEMM=f16x3p|f32.  A forward and its backward must run in the same mode. */
 int dgm_mlp_set_gemm(int mode);
+
+/* Where a grouped backward pass (dgm_mlp_backward_group) sums the weight-gradient partial tiles of its hidden layers: `pieces` of
+ * every such layer's reduction (of 256) run inside the next layer's paired launch, on workgroups that have finished their own
+ * share, the rest in the pass's final reduction launch.  0: none (the final launch does all of it); values above 256 mean all.
+ * The sums and their order are the same wherever a piece runs: the gradients do not depend on this value.  Returns the previous
+ * value; a negative argument only queries.  Process-wide; the initial value is 0 or DGM_MLP_REDUCE_IN_PAIR=<n>. */
+int dgm_mlp_set_reduce_in_pair(int pieces);
 
 /* Bytes of the workspace that forward fills (embedding, the 8 post-ReLU activations, re-laid-out
  * weights, scratch) and backward consumes; caller-owned, must stay alive between the two calls.  The same size in every
