@@ -79,7 +79,7 @@ def closest_on_mesh(points, verts, faces, max_dist=math.inf):
     bary = torch.empty((N, 3), dtype=torch.float32, device=dev)
     scratch = None
     if not math.isinf(max_d2):
-        scratch = torch.empty(int(L.dgm_surf_closest_scratch_bytes(N, F)), dtype=torch.uint8, device=dev)
+        scratch = _lib.scratch(L.dgm_surf_closest_scratch_bytes(N, F), dev)
     with _lib.device_guard(dev):
         _lib.check(L.dgm_surf_closest(N, V, F, _lib.vp(p), _lib.vp(v), _lib.vp(f), max_d2, _lib.vp(scratch), _lib.vp(face), _lib.vp(d2), _lib.vp(bary),
                                       _lib.stream_ptr()))
@@ -303,13 +303,13 @@ def export_correspondence(gaussians, deform, deform_back, mesh, out_dir, frames=
                           smooth=None, repair=None, *, t_ref=0.0, mode="reference", palette="checker", max_dist=None, n_tracks=2048, seed=0, cells=8):
     """visualize.export_dynamic_mesh's sequence (t = i / frames) with the correspondence on it, under out_dir/correspondence:
     frame_{i}.ply -- the mesh of frame i in its correspondence colours (ply_io.write_mesh_ply) --, tracks.npz -- tracks
-    (T, K, 3) float32 with NaN where unmatched, found (T, K) bool, times (T,) -- and report.json (module docstring).  clean: as
-    export_dynamic_mesh, applied to the WRITTEN meshes only (the colours follow their vertices); the snap and the tracks use the
-    full meshes.  simplify: as export_dynamic_mesh, after `clean`, on the WRITTEN meshes only; a new vertex takes the colour of its
-    cluster's representative.  smooth: as export_dynamic_mesh, on the WRITTEN meshes only, after `clean` and BEFORE `simplify`.  repair: as
-    export_dynamic_mesh, on the WRITTEN meshes only, LAST, after `simplify`; a new vertex takes the mean colour of its rim.
-    -> {"paths": [...], "tracks_path", "report_path", "report", "tracks", "found", "times"}."""
-    from . import mesh_clean, mesh_repair, mesh_simplify, mesh_smooth
+    (T, K, 3) float32 with NaN where unmatched, found (T, K) bool, times (T,) -- and report.json (module docstring).  The four stages of
+    mesh_post, each None or its spec (or a dict of its fields), change the WRITTEN meshes only, the colours following their vertices
+    (mesh_post); the snap and the tracks use the full meshes -- clean: a mesh_clean.CleanSpec, first.  simplify: a
+    mesh_simplify.SimplifySpec, after `clean`.  smooth: a mesh_smooth.SmoothSpec, after `clean` and BEFORE `simplify`.  repair: a
+    mesh_repair.RepairSpec, LAST, after `simplify`.
+    ->{"paths": [...], "tracks_path", "report_path", "report", "tracks", "found", "times"}."""
+    from . import mesh_post
     from .ply_io import write_mesh_ply
     who = "export_correspondence"
     _check_options(who, mode, palette, n_tracks, cells)
@@ -326,10 +326,7 @@ def export_correspondence(gaussians, deform, deform_back, mesh, out_dir, frames=
     for i in range(n):
         fid = torch.tensor([i / n], dtype=torch.float32, device=dev)
         verts, faces, _, corr_color, _ = tr.frame(i, fid)
-        verts, faces, corr_color = mesh_clean.apply(clean, verts, faces, corr_color)
-        verts, faces, corr_color = mesh_smooth.apply(smooth, verts, faces, corr_color)
-        verts, faces, corr_color = mesh_simplify.apply(simplify, verts, faces, corr_color)
-        verts, faces, corr_color = mesh_repair.apply(repair, verts, faces, corr_color)
+        verts, faces, corr_color = mesh_post.apply(verts, faces, corr_color, clean=clean, smooth=smooth, simplify=simplify, repair=repair)
         paths.append(os.path.join(out_dir, "correspondence", f"frame_{i}.ply"))
         write_mesh_ply(paths[-1], verts, faces, vertex_colors=corr_color)
     times = np.arange(n, dtype=np.float32) / np.float32(n)

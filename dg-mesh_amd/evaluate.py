@@ -100,15 +100,11 @@ def testing(gaussians, deform, deform_back, cameras, *, pipe, background, mesh=N
     None, "time_per_view": seconds, "fps": views per second}; the time is the wall time of the whole loop with one synchronisation
     at its end, metrics included (the reference times the two renders of each view on the host clock without synchronising).
     out_dir: writes test_results/test_result.txt, the reference's two lines (their LPIPS fields only with `lpips`), and with save_meshes
-    test_results/dynamic_mesh/frame_{idx}.ply with vertex colours (ply_io.write_mesh_ply).  clean: None, or a mesh_clean.CleanSpec
-    (or a dict of its fields): the components that fail it are removed from the WRITTEN mesh only (mesh_clean.clean_mesh, the colours
-    gathered with its vertex index); the mesh image and its metrics are those of the full mesh.  simplify: None, or a
-    mesh_simplify.SimplifySpec (or a dict of its fields): the WRITTEN mesh only is decimated by quadric vertex clustering, after
-    `clean`, the colours taken at the representatives.  smooth: None, or a mesh_smooth.SmoothSpec (or a dict of its fields): the
-    WRITTEN mesh only is smoothed (mesh_smooth.smooth_mesh), after `clean` and BEFORE `simplify` -- denoised first, decimated after.
-    repair: None, or a mesh_repair.RepairSpec (or a dict of its fields): the WRITTEN mesh only is repaired (mesh_repair.repair_mesh:
-    every body oriented consistently and outwards, small holes filled) LAST, after `simplify`; a new vertex takes the mean colour of
-    its rim.  save_glb: also writes the reference's test_results/dynamic_glb/frame_{idx}.glb (R/train.py:740), the same written mesh with its
+    test_results/dynamic_mesh/frame_{idx}.ply with vertex colours (ply_io.write_mesh_ply).  The four stages of
+    mesh_post, each None or its spec (or a dict of its fields), change the WRITTEN mesh only, its colours following their vertices
+    (mesh_post); the mesh image and its metrics are those of the full mesh -- clean: a mesh_clean.CleanSpec, first.  simplify: a
+    mesh_simplify.SimplifySpec, after `clean`.  smooth: a mesh_smooth.SmoothSpec, after `clean` and BEFORE `simplify`.  repair: a
+    mesh_repair.RepairSpec, LAST, after `simplify`.  save_glb: also writes the reference's test_results/dynamic_glb/frame_{idx}.glb (R/train.py:740), the same written mesh with its
     vertex colours as binary glTF (glb_io.write_mesh_glb); needs mesh and out_dir.
 
     lpips: None, or {"alex": lpips.LPIPS, "vgg": lpips.LPIPS} with either key optional.  Each network then scores both images of a
@@ -162,11 +158,8 @@ def testing(gaussians, deform, deform_back, cameras, *, pipe, background, mesh=N
         for j, net in enumerate(nets):
             lpips[net]._into(*LP._checked(images, gt, net), lp_table[idx, j, :images.shape[0]])
         if save_meshes or save_glb:
-            from . import mesh_clean, mesh_repair, mesh_simplify, mesh_smooth
-            w_verts, w_faces, w_color = mesh_clean.apply(clean, verts, faces, vtx_color)
-            w_verts, w_faces, w_color = mesh_smooth.apply(smooth, w_verts, w_faces, w_color)
-            w_verts, w_faces, w_color = mesh_simplify.apply(simplify, w_verts, w_faces, w_color)
-            w_verts, w_faces, w_color = mesh_repair.apply(repair, w_verts, w_faces, w_color)
+            from . import mesh_post
+            w_verts, w_faces, w_color = mesh_post.apply(verts, faces, vtx_color, clean=clean, smooth=smooth, simplify=simplify, repair=repair)
             if save_meshes:
                 from .ply_io import write_mesh_ply
                 write_mesh_ply(os.path.join(saving_path, "dynamic_mesh", f"frame_{idx}.ply"), w_verts, w_faces, vertex_colors=w_color)

@@ -17,7 +17,7 @@ from dataclasses import dataclass
 
 import torch
 
-from . import _lib
+from . import _lib, mesh_args
 
 
 @dataclass(frozen=True)
@@ -38,11 +38,7 @@ class CleanSpec:
 
 def as_spec(clean):
     """None, a CleanSpec or a dict of its fields -> CleanSpec or None ("do nothing")."""
-    if clean is None or isinstance(clean, CleanSpec):
-        return clean
-    if isinstance(clean, dict):
-        return CleanSpec(**clean)
-    raise TypeError(f"mesh_clean: clean must be None, a CleanSpec or a dict of its fields, got {type(clean).__name__}")
+    return mesh_args.spec_of("mesh_clean", "clean", CleanSpec, clean)
 
 
 def tile():
@@ -50,35 +46,11 @@ def tile():
     return int(_lib.lib().dgm_mesh_clean_tile())
 
 
-def _faces(name, faces):
-    if not torch.is_tensor(faces) or not faces.is_cuda:
-        raise RuntimeError(f"mesh_clean.{name} needs CUDA/HIP tensors (dg-mesh_amd has no CPU path)")
-    if faces.dtype != torch.int32:
-        raise RuntimeError(f"mesh_clean.{name}: faces must be int32, got {faces.dtype}")
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"mesh_clean.{name}: faces must be (F, 3), got {tuple(faces.shape)}")
-    return faces.detach().contiguous()
-
-
-def _verts(name, verts, dev=None):
-    if not torch.is_tensor(verts) or not verts.is_cuda:
-        raise RuntimeError(f"mesh_clean.{name} needs CUDA/HIP tensors (dg-mesh_amd has no CPU path)")
-    if verts.dtype != torch.float32:
-        raise RuntimeError(f"mesh_clean.{name}: verts must be float32, got {verts.dtype}")
-    if verts.dim() != 2 or verts.shape[1] != 3:
-        raise ValueError(f"mesh_clean.{name}: verts must be (V, 3), got {tuple(verts.shape)}")
-    if dev is not None and verts.device != dev:
-        raise ValueError(f"mesh_clean.{name}: verts on {verts.device}, faces on {dev}")
-    return verts.detach().contiguous()
-
-
 def connected_components(faces, num_verts):
     """labels (num_verts,) int32: the smallest vertex index of each vertex's component.  Faces with a repeated index connect nothing;
     a face with an index outside [0, num_verts) raises ValueError naming their count (the kernel range-checks before it indexes)."""
-    faces = _faces("connected_components", faces)
+    faces = mesh_args.faces("mesh_clean.connected_components", faces, num_verts)
     V, F = int(num_verts), int(faces.shape[0])
-    if V < 0:
-        raise ValueError(f"mesh_clean.connected_components: num_verts must be >= 0, got {num_verts}")
     L = _lib.lib()
     dev = faces.device
     labels = torch.empty(V, dtype=torch.int32, device=dev)
@@ -104,21 +76,12 @@ def _stats(verts, faces, labels):
     return comp_faces, comp_verts, comp_bbox
 
 
-def _labels(name, labels, V, dev):
-    if not torch.is_tensor(labels) or not labels.is_cuda:
-        raise RuntimeError(f"mesh_clean.{name} needs CUDA/HIP tensors (dg-mesh_amd has no CPU path)")
-    if labels.dtype != torch.int32 or tuple(labels.shape) != (V,) or labels.device != dev:
-        raise ValueError(f"mesh_clean.{name}: labels must be ({V},) int32 on {dev}")
-    return labels.contiguous()
-
-
 def component_table(verts, faces, labels=None):
     """One row per component, ordered by label: {"label", "faces" (valid faces), "verts": (C,) int32, "bbox_min", "bbox_max":
     (C, 3) float32}, device tensors.  labels: connected_components' (computed when None)."""
-    faces = _faces("component_table", faces)
-    verts = _verts("component_table", verts, faces.device)
+    verts, faces = mesh_args.mesh("mesh_clean.component_table", verts, faces)
     V = int(verts.shape[0])
-    labels = connected_components(faces, V) if labels is None else _labels("component_table", labels, V, faces.device)
+    labels = connected_components(faces, V) if labels is None else mesh_args.labels("mesh_clean.component_table", labels, V, faces.device)
     comp_faces, comp_verts, comp_bbox = _stats(verts, faces, labels)
     roots = torch.nonzero(comp_verts > 0).flatten()
     return {"label": roots.to(torch.int32), "faces": comp_faces[roots], "verts": comp_verts[roots],
@@ -127,13 +90,12 @@ def component_table(verts, faces, labels=None):
 
 def keep_mask(verts, faces, labels=None, *, largest=False, min_faces=0, min_diameter_frac=0.0):
     """(F,) uint8, 1 for the faces clean_mesh keeps."""
-    faces = _faces("keep_mask", faces)
-    verts = _verts("keep_mask", verts, faces.device)
+    verts, faces = mesh_args.mesh("mesh_clean.keep_mask", verts, faces)
     if int(min_faces) < 0 or not float(min_diameter_frac) >= 0.0:
         raise ValueError(f"mesh_clean: need min_faces >= 0 and min_diameter_frac >= 0, got {min_faces} and {min_diameter_frac}")
     L = _lib.lib()
     V, F, dev = int(verts.shape[0]), int(faces.shape[0]), faces.device
-    labels = connected_components(faces, V) if labels is None else _labels("keep_mask", labels, V, dev)
+    labels = connected_components(faces, V) if labels is None else mesh_args.labels("mesh_clean.keep_mask", labels, V, dev)
     comp_faces, comp_verts, comp_bbox = _stats(verts, faces, labels)
     keep = torch.empty(F, dtype=torch.uint8, device=dev)
     scratch = _lib.scratch(L.dgm_mesh_cc_select_scratch_bytes(), dev)
@@ -147,8 +109,7 @@ def keep_mask(verts, faces, labels=None, *, largest=False, min_faces=0, min_diam
 def compact(verts, faces, keep):
     """The faces with keep != 0 and the vertices they use, in their old order: (verts', faces' re-indexed, vert_index, face_index),
     the last two int32, the old index of each survivor.  One 8-byte read-back (the sizes)."""
-    faces = _faces("compact", faces)
-    verts = _verts("compact", verts, faces.device)
+    verts, faces = mesh_args.mesh("mesh_clean.compact", verts, faces)
     V, F, dev = int(verts.shape[0]), int(faces.shape[0]), faces.device
     if not torch.is_tensor(keep) or keep.device != dev or keep.dtype not in (torch.uint8, torch.bool) or tuple(keep.shape) != (F,):
         raise ValueError(f"mesh_clean.compact: keep must be ({F},) uint8 or bool on {dev}")

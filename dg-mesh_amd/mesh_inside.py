@@ -23,30 +23,10 @@ import math
 
 import torch
 
-from . import _lib
+from . import _lib, mesh_args
 
 SCRATCH_LIMIT = 64 << 20  # bytes of slice sums per launch; more queries are taken in batches (the result does not depend on them)
 SLICE_FACES = 16384       # WN_SLICE of csrc/mesh_inside.hip
-
-
-def _need(name, t, what, dtype):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"mesh_inside.{name}: {what} must be a CUDA/HIP tensor (dg-mesh_amd has no CPU path)")
-    if t.dtype != dtype:
-        raise RuntimeError(f"mesh_inside.{name}: {what} must be {dtype}, got {t.dtype}")
-    if t.dim() != 2 or t.shape[1] != 3:
-        raise ValueError(f"mesh_inside.{name}: {what} must be (n, 3), got {tuple(t.shape)}")
-
-
-def _mesh(name, verts, faces, *more):
-    _need(name, verts, "verts", torch.float32)
-    _need(name, faces, "faces", torch.int32)
-    for what, t in more:
-        _need(name, t, what, torch.float32)
-    for t in (faces,) + tuple(t for _, t in more):
-        if t.device != verts.device:
-            raise ValueError(f"mesh_inside.{name}: tensors on {verts.device} and {t.device}")
-    return verts.detach().contiguous(), faces.contiguous()
 
 
 def batch_rows(F):
@@ -60,8 +40,7 @@ def winding_number(points, verts, faces):
     the definition and in the summation order of include/dgmesh_hip.h.  A face with an index outside [0, V), a non-finite corner or
     no volume against the query adds nothing; a query with a non-finite coordinate gets NaN; F = 0 or V = 0 gives 0.  N x F pairs;
     large N is taken in batches, which changes no bit."""
-    name = "winding_number"
-    v, f = _mesh(name, verts, faces, ("points", points))
+    v, f = mesh_args.mesh("mesh_inside.winding_number", verts, faces, ("points", points))
     p = points.detach().contiguous()
     N, V, F = p.shape[0], v.shape[0], f.shape[0]
     L = _lib.lib()
@@ -70,7 +49,7 @@ def winding_number(points, verts, faces):
     with _lib.device_guard(p.device):
         for at in range(0, N, step):
             n = min(step, N - at)
-            scratch = torch.empty(int(L.dgm_wind_scratch_bytes(n, F)), dtype=torch.uint8, device=p.device)
+            scratch = _lib.scratch(L.dgm_wind_scratch_bytes(n, F), p.device)
             _lib.check(L.dgm_wind_number(n, V, F, _lib.vp(p[at:at + n]), _lib.vp(v), _lib.vp(f), _lib.vp(scratch), _lib.vp(w[at:at + n]), _lib.stream_ptr()))
     return w
 
@@ -89,7 +68,7 @@ def signed_distance(points, verts, faces, max_dist=math.inf, absolute=False):
     sqrt(d2) of correspondence.closest_on_mesh(points, verts, faces, max_dist) -- the same kernel, the same bits --, so a query
     with no face within max_dist gets +inf outside and -inf inside."""
     from .correspondence import closest_on_mesh
-    _mesh("signed_distance", verts, faces, ("points", points))
+    mesh_args.mesh("mesh_inside.signed_distance", verts, faces, ("points", points))
     dist = closest_on_mesh(points, verts, faces, max_dist)[1].sqrt()
     return torch.where(contains(points, verts, faces, absolute=absolute), -dist, dist)
 
@@ -122,7 +101,7 @@ def occupancy_grid(verts, faces, res, lo=None, hi=None, absolute=False):
     device tensors each); the default box is the bounding box of verts.  Cost: res^3 x F pairs -- every cell visits every face; a
     128^3 grid against 261 k faces is 5.5 10^11 pairs, about a second."""
     name = "occupancy_grid"
-    v, f = _mesh(name, verts, faces)
+    v, f = mesh_args.mesh(f"mesh_inside.{name}", verts, faces)
     res = int(res)
     if res < 1:
         raise ValueError(f"mesh_inside.{name}: res must be >= 1, got {res}")
@@ -138,8 +117,8 @@ def volume_iou(verts_a, faces_a, verts_b, faces_b, n_points=100000, generator=No
     "n_a", "n_b", "n_inter", "n_union" (int64), "volume_a", "volume_b" (fp64: box volume x share of the samples); with
     return_points=True also "points" (n_points, 3)."""
     name = "volume_iou"
-    va, fa = _mesh(name, verts_a, faces_a)
-    vb, fb = _mesh(name, verts_b, faces_b)
+    va, fa = mesh_args.mesh(f"mesh_inside.{name}", verts_a, faces_a)
+    vb, fb = mesh_args.mesh(f"mesh_inside.{name}", verts_b, faces_b)
     if va.device != vb.device:
         raise ValueError(f"mesh_inside.{name}: meshes on {va.device} and {vb.device}")
     n_points = int(n_points)

@@ -26,31 +26,11 @@ import math
 
 import torch
 
-from . import _lib
+from . import _lib, mesh_args
 
 AUTO_MIN_FACES = 752       # accel="auto": the structure from this many faces on, the smallest mesh on which tools/mesh_ray_bench.py
                            # showed build + accelerated cast ahead of the brute force for one 800 x 800 cast
 RAY_BATCH = 1 << 22        # rays per launch of ambient_occlusion (memory only: the result does not depend on it)
-
-
-def _need(name, t, what, dtype):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"mesh_ray.{name}: {what} must be a CUDA/HIP tensor (dg-mesh_amd has no CPU path)")
-    if t.dtype != dtype:
-        raise RuntimeError(f"mesh_ray.{name}: {what} must be {dtype}, got {t.dtype}")
-    if t.dim() != 2 or t.shape[1] != 3:
-        raise ValueError(f"mesh_ray.{name}: {what} must be (n, 3), got {tuple(t.shape)}")
-
-
-def _mesh(name, verts, faces, *more):
-    _need(name, verts, "verts", torch.float32)
-    _need(name, faces, "faces", torch.int32)
-    for what, t in more:
-        _need(name, t, what, torch.float32)
-    for t in (faces,) + tuple(t for _, t in more):
-        if t.device != verts.device:
-            raise ValueError(f"mesh_ray.{name}: tensors on {verts.device} and {t.device}")
-    return verts.detach().contiguous(), faces.contiguous()
 
 
 class RayMesh:
@@ -59,13 +39,13 @@ class RayMesh:
     ray_cast, occluded, ... as `accel`; the answers are those of the brute force bit for bit."""
 
     def __init__(self, verts, faces):
-        self.verts, self.faces = _mesh("RayMesh", verts, faces)
+        self.verts, self.faces = mesh_args.mesh("mesh_ray.RayMesh", verts, faces)
         V, F = self.verts.shape[0], self.faces.shape[0]
         L = _lib.lib()
         dev = self.verts.device
         self.accel = torch.empty(int(L.dgm_ray_accel_bytes(F)), dtype=torch.uint8, device=dev)
         with _lib.device_guard(dev):
-            scratch = torch.empty(int(L.dgm_ray_build_scratch_bytes(F)), dtype=torch.uint8, device=dev)
+            scratch = _lib.scratch(L.dgm_ray_build_scratch_bytes(F), dev)
             _lib.check(L.dgm_ray_build(V, F, _lib.vp(self.verts), _lib.vp(self.faces), _lib.vp(scratch), _lib.vp(self.accel), _lib.stream_ptr()))
 
 
@@ -75,7 +55,7 @@ def _resolve(name, verts, faces, accel):
         if verts is not None and (tuple(verts.shape) != tuple(accel.verts.shape) or tuple(faces.shape) != tuple(accel.faces.shape)):
             raise ValueError(f"mesh_ray.{name}: the RayMesh was built for another mesh ({tuple(accel.verts.shape)}, {tuple(accel.faces.shape)})")
         return accel.verts, accel.faces, accel
-    v, f = _mesh(name, verts, faces)
+    v, f = mesh_args.mesh(f"mesh_ray.{name}", verts, faces)
     if accel is None:
         return v, f, None
     if isinstance(accel, str) and accel == "auto":
@@ -88,13 +68,12 @@ def _accel_ptr(held):
 
 
 def _rays(name, origins, dirs, v):
-    _need(name, origins, "origins", torch.float32)
-    _need(name, dirs, "dirs", torch.float32)
+    who = f"mesh_ray.{name}"
+    mesh_args.need(who, origins, "origins", torch.float32)
+    mesh_args.need(who, dirs, "dirs", torch.float32)
     if origins.shape != dirs.shape:
-        raise ValueError(f"mesh_ray.{name}: origins {tuple(origins.shape)} and dirs {tuple(dirs.shape)} differ")
-    for t in (origins, dirs):
-        if t.device != v.device:
-            raise ValueError(f"mesh_ray.{name}: tensors on {v.device} and {t.device}")
+        raise ValueError(f"{who}: origins {tuple(origins.shape)} and dirs {tuple(dirs.shape)} differ")
+    mesh_args.one_device(who, ("verts", v), ("origins", origins), ("dirs", dirs))
     return origins.detach().contiguous(), dirs.detach().contiguous()
 
 
@@ -139,8 +118,7 @@ def hit_points(origins, dirs, t):
 def visible(points, eye, verts, faces, eps=1e-4, accel="auto"):
     """(N,) bool: no face is hit on the way from points (N, 3) to eye ((3,) or (N, 3)) with t in [eps, 1 - eps) along eye - point
     (eps keeps the surface a point lies on, and one the eye lies on, from hiding it)."""
-    name = "visible"
-    _need(name, points, "points", torch.float32)
+    mesh_args.need("mesh_ray.visible", points, "points", torch.float32)
     eye = torch.as_tensor(eye, dtype=torch.float32).to(points.device)
     dirs = (eye.reshape(-1, 3) - points).contiguous()
     return ~occluded(points, dirs, verts, faces, float(eps), 1.0 - float(eps), accel)
@@ -179,7 +157,7 @@ def camera_rays(camera, device=None):
 def depth_map(camera, verts, faces, accel="auto"):
     """(depth (H, W) fp32, face (H, W) int32): the view-space depth of the nearest face along the ray through every pixel centre
     (camera_rays), +inf and -1 on the background."""
-    _mesh("depth_map", verts, faces)
+    mesh_args.mesh("mesh_ray.depth_map", verts, faces)
     o, d = camera_rays(camera, verts.device)
     face, t, _ = ray_cast(o, d, verts, faces, 0.0, math.inf, accel)
     H, W = int(camera.image_height), int(camera.image_width)
@@ -255,7 +233,7 @@ def ambient_occlusion(points, normals, verts, faces, samples=64, max_dist=math.i
     if samples < 1:
         raise ValueError(f"mesh_ray.{name}: samples must be >= 1, got {samples}")
     v, f, held = _resolve(name, verts, faces, accel)
-    _mesh(name, v, f, ("points", points), ("normals", normals))
+    mesh_args.mesh(f"mesh_ray.{name}", v, f, ("points", points), ("normals", normals))
     if points.shape != normals.shape:
         raise ValueError(f"mesh_ray.{name}: points {tuple(points.shape)} and normals {tuple(normals.shape)} differ")
     lifted = ao_origins(points, normals, v, offset)
@@ -275,7 +253,7 @@ def vertex_ambient_occlusion(verts, faces, samples=64, max_dist=math.inf, offset
     run, and with it the rotation of that vertex's set); flip=True negates them, for a mesh wound inwards.  A vertex without a normal
     (unreferenced) gets 1."""
     from .visualize import vertex_normals
-    v, f = _mesh("vertex_ambient_occlusion", verts, faces)
+    v, f = mesh_args.mesh("mesh_ray.vertex_ambient_occlusion", verts, faces)
     normals = vertex_normals(v, f)
     if flip:
         normals = -normals
@@ -295,14 +273,11 @@ def build_parser():
 
 
 def main(argv=None):
-    from .ply_io import read_mesh_ply, write_mesh_ply
+    from .ply_io import read_mesh_ply_on_device, write_mesh_ply
     args = build_parser().parse_args(argv)
-    dev = torch.device("cuda", torch.cuda.current_device())
-    verts, faces, colors = read_mesh_ply(args.mesh, return_colors=True)
-    v, f = torch.from_numpy(verts).to(dev), torch.from_numpy(faces).to(dev)
-    ao = vertex_ambient_occlusion(v, f, samples=args.samples, max_dist=args.max_dist, seed=args.seed, flip=args.flip)
-    # (the byte k is read as (k + 0.5) / 255, as mesh_texture reads it: an ambient occlusion of 1 gives the byte back)
-    base = (torch.from_numpy(colors[:, :3].copy()).to(dev).float() + 0.5) / 255.0 if colors is not None else torch.ones_like(v)
+    verts, faces, colors = read_mesh_ply_on_device(args.mesh, torch.device("cuda", torch.cuda.current_device()))
+    ao = vertex_ambient_occlusion(verts, faces, samples=args.samples, max_dist=args.max_dist, seed=args.seed, flip=args.flip)
+    base = colors if colors is not None else torch.ones_like(verts)  # (an ambient occlusion of 1 gives the file's byte back)
     write_mesh_ply(args.ao, verts, faces, vertex_colors=base * ao[:, None])
     print(f"mesh_ray: V {len(verts)} F {len(faces)}  samples {args.samples}  mean ambient occlusion {float(ao.mean()) if len(verts) else 1.0:.4f}  -> {args.ao}")
     return 0

@@ -31,10 +31,9 @@ import argparse
 import json
 from dataclasses import dataclass
 
-import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, mesh_args
 
 ORIENT_FIELDS = ("components", "closed_components", "unorientable_components", "faces_flipped", "components_inverted", "outward_skipped")
 FILL_FIELDS = ("boundary_edges", "holes_filled", "holes_too_long", "edges_on_open_chains", "verts_added", "faces_added")
@@ -53,24 +52,7 @@ class RepairSpec:
 
 def as_spec(repair):
     """None, a RepairSpec or a dict of its fields -> RepairSpec or None ("do nothing")."""
-    if repair is None or isinstance(repair, RepairSpec):
-        return repair
-    if isinstance(repair, dict):
-        return RepairSpec(**repair)
-    raise TypeError(f"mesh_repair: repair must be None, a RepairSpec or a dict of its fields, got {type(repair).__name__}")
-
-
-def _mesh(name, verts, faces):
-    for t in (verts, faces):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise RuntimeError(f"mesh_repair.{name} needs CUDA/HIP tensors (dg-mesh_amd has no CPU path)")
-    if verts.dtype != torch.float32 or faces.dtype != torch.int32:
-        raise RuntimeError(f"mesh_repair.{name}: verts must be float32 and faces int32, got {verts.dtype} and {faces.dtype}")
-    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"mesh_repair.{name}: verts must be (V, 3) and faces (F, 3), got {tuple(verts.shape)} and {tuple(faces.shape)}")
-    if verts.device != faces.device:
-        raise ValueError(f"mesh_repair.{name}: verts on {verts.device}, faces on {faces.device}")
-    return verts.detach().contiguous(), faces.detach().contiguous()
+    return mesh_args.spec_of("mesh_repair", "repair", RepairSpec, repair)
 
 
 def _max_hole_edges(n):
@@ -126,7 +108,7 @@ def orient_faces(verts, faces, *, outward=True):
     info: {"components", "closed_components", "unorientable_components", "faces_flipped", "components_inverted": closed components that
     the volume rule turned against the orientation that keeps their smallest face, "outward_skipped": 1 when outward was asked for and
     the box of the used vertices is not finite or has no extent (the volume rule is then skipped for the whole mesh)}."""
-    verts, faces = _mesh("orient_faces", verts, faces)
+    verts, faces = mesh_args.mesh("mesh_repair.orient_faces", verts, faces)
     faces_out, flipped, info = _orient(_table("orient_faces", verts, faces), verts, faces, bool(outward))
     return faces_out, flipped.bool(), info
 
@@ -141,7 +123,7 @@ def fill_holes(verts, faces, *, max_hole_edges=1000):
     boundary edges on rims that pass a vertex where more than one rim meets, "verts_added", "faces_added"}."""
     n = _max_hole_edges(max_hole_edges)
     given = (verts, faces)
-    verts, faces = _mesh("fill_holes", verts, faces)
+    verts, faces = mesh_args.mesh("mesh_repair.fill_holes", verts, faces)
     v, f, info = _fill(_table("fill_holes", verts, faces), verts, faces, None, n)
     return (given[0] if v is verts else v, given[1] if f is faces else f, info)
 
@@ -152,7 +134,7 @@ def repair_mesh(verts, faces, *, orient=True, outward=True, max_hole_edges=1000)
     fill_holes alone)."""
     n = _max_hole_edges(max_hole_edges)
     given = (verts, faces)
-    verts, faces = _mesh("repair_mesh", verts, faces)
+    verts, faces = mesh_args.mesh("mesh_repair.repair_mesh", verts, faces)
     table = _table("repair_mesh", verts, faces)
     info, flipped, oriented = {}, None, faces
     if orient:
@@ -209,18 +191,13 @@ def spec_from_args(args):
 
 
 def main(argv=None):
-    from .ply_io import read_mesh_ply, write_mesh_ply
+    from .ply_io import read_mesh_ply_on_device, write_mesh_ply
     args = build_parser().parse_args(argv)
     spec = spec_from_args(args)
     _max_hole_edges(spec.max_hole_edges)
-    verts, faces, colors = read_mesh_ply(args.input, return_colors=True)
-    dev = torch.device("cuda")
-    v, f = torch.from_numpy(verts).to(dev), torch.from_numpy(faces).to(dev)
-    # (write_mesh_ply quantises floats in [0, 1] as clip(c * 255) truncated: (k + 0.5) / 255 gives k back for every byte k)
-    c = None if colors is None else torch.from_numpy((colors[:, :3].astype(np.float32) + np.float32(0.5)) / np.float32(255.0)).to(dev)
-    (v2, f2, c2), info = apply_with_info(spec, v, f, c)
-    write_mesh_ply(args.output, v2.cpu().numpy(), f2.cpu().numpy(), vertex_colors=None if c2 is None else c2.cpu().numpy())
-    print(json.dumps({"input": args.input, "output": args.output, "verts": int(v2.shape[0]), "faces": int(f2.shape[0]), **info}))
+    (v, f, c), info = apply_with_info(spec, *read_mesh_ply_on_device(args.input, torch.device("cuda")))
+    write_mesh_ply(args.output, v, f, vertex_colors=c)
+    print(json.dumps({"input": args.input, "output": args.output, "verts": int(v.shape[0]), "faces": int(f.shape[0]), **info}))
     return 0
 
 

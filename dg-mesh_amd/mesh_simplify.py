@@ -34,7 +34,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, mesh_args
 
 MAX_DIM = 1 << 20
 GRID_RANGE = (2, 1024)
@@ -56,24 +56,7 @@ class SimplifySpec:
 
 def as_spec(simplify):
     """None, a SimplifySpec or a dict of its fields -> SimplifySpec or None ("do nothing")."""
-    if simplify is None or isinstance(simplify, SimplifySpec):
-        return simplify
-    if isinstance(simplify, dict):
-        return SimplifySpec(**simplify)
-    raise TypeError(f"mesh_simplify: simplify must be None, a SimplifySpec or a dict of its fields, got {type(simplify).__name__}")
-
-
-def _mesh(verts, faces):
-    for t in (verts, faces):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise RuntimeError("mesh_simplify.simplify_mesh needs CUDA/HIP tensors (dg-mesh_amd has no CPU path)")
-    if verts.dtype != torch.float32 or faces.dtype != torch.int32:
-        raise RuntimeError(f"mesh_simplify.simplify_mesh: verts must be float32 and faces int32, got {verts.dtype} and {faces.dtype}")
-    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"mesh_simplify.simplify_mesh: verts must be (V, 3) and faces (F, 3), got {tuple(verts.shape)} and {tuple(faces.shape)}")
-    if verts.device != faces.device:
-        raise ValueError(f"mesh_simplify.simplify_mesh: verts on {verts.device}, faces on {faces.device}")
-    return verts.detach().contiguous(), faces.detach().contiguous()
+    return mesh_args.spec_of("mesh_simplify", "simplify", SimplifySpec, simplify)
 
 
 def _choice(cell, grid, target_faces, regularization):
@@ -212,7 +195,7 @@ def simplify_mesh(verts, faces, *, cell=None, grid=None, target_faces=None, regu
     target_faces is given; target_faces bisects grid over [2, 1024] with at most 10 count-only passes and keeps the finest grid tried
     whose face count is <= the target (ValueError when even grid = 2 leaves more).  An empty result has (0, 3) tensors."""
     _choice(cell, grid, target_faces, regularization)
-    verts, faces = _mesh(verts, faces)
+    verts, faces = mesh_args.mesh("mesh_simplify.simplify_mesh", verts, faces)
     p = _Pass(verts, faces, states=2 if target_faces is not None else 1)
     tried = []
     if target_faces is not None:
@@ -266,17 +249,13 @@ def spec_from_args(args):
 
 
 def main(argv=None):
-    from .ply_io import read_mesh_ply, write_mesh_ply
+    from .ply_io import read_mesh_ply_on_device, write_mesh_ply
     args = build_parser().parse_args(argv)
     spec = spec_from_args(args)
-    verts, faces, colors = read_mesh_ply(args.input, return_colors=True)
-    dev = torch.device("cuda")
-    v, f, vi, _, _, info = simplify_mesh(torch.from_numpy(verts).to(dev), torch.from_numpy(faces).to(dev), cell=spec.cell, grid=spec.grid,
-                                         target_faces=spec.target_faces, regularization=spec.regularization, return_index=True,
-                                         return_info=True)
-    # (write_mesh_ply quantises floats in [0, 1] as clip(c * 255) truncated: (k + 0.5) / 255 gives k back for every byte k)
-    new_colors = None if colors is None else (colors[vi.cpu().numpy(), :3].astype(np.float32) + np.float32(0.5)) / np.float32(255.0)
-    write_mesh_ply(args.output, v, f, vertex_colors=new_colors)
+    verts, faces, colors = read_mesh_ply_on_device(args.input, torch.device("cuda"))
+    v, f, vi, _, _, info = simplify_mesh(verts, faces, cell=spec.cell, grid=spec.grid, target_faces=spec.target_faces,
+                                         regularization=spec.regularization, return_index=True, return_info=True)
+    write_mesh_ply(args.output, v, f, vertex_colors=None if colors is None else colors[vi.long()])
     print(f"mesh_simplify: V {len(verts)} F {len(faces)} -> V {v.shape[0]} F {f.shape[0]}  cell {info['cell']:g} dims {info['dims']}"
           + (f" grid {info['grid']}" if info["grid"] is not None else "") + f"  count passes {info['count_passes']}")
     return 0

@@ -26,7 +26,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, mesh_args
 
 METHODS = ("taubin", "laplacian")
 BOUNDARIES = ("fixed", "curve", "free")  # the int of the C ABI is the index
@@ -47,24 +47,7 @@ class SmoothSpec:
 
 def as_spec(smooth):
     """None, a SmoothSpec or a dict of its fields -> SmoothSpec or None ("do nothing")."""
-    if smooth is None or isinstance(smooth, SmoothSpec):
-        return smooth
-    if isinstance(smooth, dict):
-        return SmoothSpec(**smooth)
-    raise TypeError(f"mesh_smooth: smooth must be None, a SmoothSpec or a dict of its fields, got {type(smooth).__name__}")
-
-
-def _mesh(verts, faces):
-    for t in (verts, faces):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise RuntimeError("mesh_smooth.smooth_mesh needs CUDA/HIP tensors (dg-mesh_amd has no CPU path)")
-    if verts.dtype != torch.float32 or faces.dtype != torch.int32:
-        raise RuntimeError(f"mesh_smooth.smooth_mesh: verts must be float32 and faces int32, got {verts.dtype} and {faces.dtype}")
-    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"mesh_smooth.smooth_mesh: verts must be (V, 3) and faces (F, 3), got {tuple(verts.shape)} and {tuple(faces.shape)}")
-    if verts.device != faces.device:
-        raise ValueError(f"mesh_smooth.smooth_mesh: verts on {verts.device}, faces on {faces.device}")
-    return verts.detach().contiguous(), faces.detach().contiguous()
+    return mesh_args.spec_of("mesh_smooth", "smooth", SmoothSpec, smooth)
 
 
 def _choice(iterations, lam, mu, method, boundary):
@@ -91,7 +74,7 @@ def smooth_mesh(verts, faces, *, iterations=10, lam=0.5, mu=-0.53, method="taubi
     mu >= -lam."""
     _choice(iterations, lam, mu, method, boundary)
     given = verts
-    verts, faces = _mesh(verts, faces)
+    verts, faces = mesh_args.mesh("mesh_smooth.smooth_mesh", verts, faces)
     factors = step_factors(iterations, lam, mu, method)
     V = int(verts.shape[0])
     if not factors or V == 0:
@@ -139,16 +122,12 @@ def spec_from_args(args):
 
 
 def main(argv=None):
-    from .ply_io import read_mesh_ply, write_mesh_ply
+    from .ply_io import read_mesh_ply_on_device, write_mesh_ply
     args = build_parser().parse_args(argv)
     spec = spec_from_args(args)
     _choice(spec.iterations, spec.lam, spec.mu, spec.method, spec.boundary)
-    verts, faces, colors = read_mesh_ply(args.input, return_colors=True)
-    dev = torch.device("cuda")
-    v = apply(spec, torch.from_numpy(verts).to(dev), torch.from_numpy(faces).to(dev))[0]
-    # (write_mesh_ply quantises floats in [0, 1] as clip(c * 255) truncated: (k + 0.5) / 255 gives k back for every byte k)
-    same_colors = None if colors is None else (colors[:, :3].astype(np.float32) + np.float32(0.5)) / np.float32(255.0)
-    write_mesh_ply(args.output, v, faces, vertex_colors=same_colors)
+    verts, faces, colors = read_mesh_ply_on_device(args.input, torch.device("cuda"))
+    write_mesh_ply(args.output, apply(spec, verts, faces)[0], faces, vertex_colors=colors)
     print(f"mesh_smooth: V {len(verts)} F {len(faces)}  {spec.describe()}")
     return 0
 

@@ -39,10 +39,9 @@ import os
 from dataclasses import dataclass
 from typing import NamedTuple, Optional
 
-import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, mesh_args
 
 MAX_SIZE = 16384
 MIN_CELL = 4
@@ -75,12 +74,7 @@ class TextureSpec:
 
 def as_spec(texture):
     """None, a TextureSpec or a dict of its fields -> TextureSpec or None ("do nothing")."""
-    if texture is None or isinstance(texture, TextureSpec):
-        spec = texture
-    elif isinstance(texture, dict):
-        spec = TextureSpec(**texture)
-    else:
-        raise TypeError(f"mesh_texture: texture must be None, a TextureSpec or a dict of its fields, got {type(texture).__name__}")
+    spec = mesh_args.spec_of("mesh_texture", "texture", TextureSpec, texture)
     if spec is not None and spec.format not in FORMATS:
         raise ValueError(f"mesh_texture: format must be one of {', '.join(FORMATS)}, got {spec.format!r}")
     if spec is not None and int(spec.ao_samples) < 0:
@@ -248,22 +242,18 @@ def build_parser():
 
 
 def main(argv=None):
-    from .ply_io import read_mesh_ply
+    from .ply_io import read_mesh_ply_on_device
     args = build_parser().parse_args(argv)
     stem, ext = os.path.splitext(args.output)
     if ext.lower() not in (".obj", ".glb"):
         raise SystemExit(f"mesh_texture: the output must end in .obj or .glb, got {args.output}")
-    verts, faces, colors = read_mesh_ply(args.input, return_colors=True)
+    verts, faces, colors = read_mesh_ply_on_device(args.input, torch.device("cuda"))
     if colors is None:
         raise SystemExit(f"mesh_texture: {args.input} has no vertex colours to bake")
-    dev = torch.device("cuda")
-    # (the byte k is stored as (k + 0.5) / 255: the writers' clamp(c * 255) truncated gives k back at the vertices)
-    col = (colors[:, :3].astype(np.float32) + np.float32(0.5)) / np.float32(255.0)
-    v, f = torch.from_numpy(verts).to(dev), torch.from_numpy(faces).to(dev)
     if args.ao < 0:
         raise SystemExit(f"mesh_texture: --ao must be >= 0, got {args.ao}")
-    tex, uv, atlas = bake_vertex_colors(v, f, torch.from_numpy(col).to(dev), size=args.size, cell=args.cell)
-    tex = apply_ambient_occlusion(tex, v, f, args.ao, size=args.size, cell=args.cell)
+    tex, uv, atlas = bake_vertex_colors(verts, faces, colors, size=args.size, cell=args.cell)
+    tex = apply_ambient_occlusion(tex, verts, faces, args.ao, size=args.size, cell=args.cell)
     out = write_textured(stem, ext.lower()[1:], verts, faces, uv, tex)
     print(f"mesh_texture: V {len(verts)} F {len(faces)}  size {atlas.size} cell {atlas.cell}  -> {out}")
     return 0

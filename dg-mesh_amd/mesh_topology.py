@@ -24,22 +24,10 @@ import json
 
 import torch
 
-from . import _lib
+from . import _lib, mesh_args
 
 INFO_FIELDS = ("edges", "boundary_edges", "nonmanifold_edges", "misoriented_edges", "regular_edges", "verts_used", "faces_valid",
                "adjacency")
-
-
-def _faces(name, faces, num_verts):
-    if not torch.is_tensor(faces) or not faces.is_cuda:
-        raise RuntimeError(f"mesh_topology.{name} needs CUDA/HIP tensors (dg-mesh_amd has no CPU path)")
-    if faces.dtype != torch.int32:
-        raise RuntimeError(f"mesh_topology.{name}: faces must be int32, got {faces.dtype}")
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"mesh_topology.{name}: faces must be (F, 3), got {tuple(faces.shape)}")
-    if int(num_verts) < 0:
-        raise ValueError(f"mesh_topology.{name}: num_verts must be >= 0, got {num_verts}")
-    return faces.detach().contiguous()
 
 
 class EdgeTable:
@@ -47,7 +35,7 @@ class EdgeTable:
     emit() then writes the tables asked for.  info: {field of INFO_FIELDS: int}."""
 
     def __init__(self, name, faces, num_verts):
-        faces = _faces(name, faces, num_verts)
+        faces = mesh_args.faces(f"mesh_topology.{name}", faces, num_verts)
         self.L = L = _lib.lib()
         self.V, self.F, self.dev = int(num_verts), int(faces.shape[0]), faces.device
         V, F, dev = self.V, self.F, self.dev
@@ -95,18 +83,6 @@ def vertex_flags(faces, num_verts):
     return EdgeTable("vertex_flags", faces, num_verts).vert_flag
 
 
-def _verts(name, verts, dev):
-    if not torch.is_tensor(verts) or not verts.is_cuda:
-        raise RuntimeError(f"mesh_topology.{name} needs CUDA/HIP tensors (dg-mesh_amd has no CPU path)")
-    if verts.dtype != torch.float32:
-        raise RuntimeError(f"mesh_topology.{name}: verts must be float32, got {verts.dtype}")
-    if verts.dim() != 2 or verts.shape[1] != 3:
-        raise ValueError(f"mesh_topology.{name}: verts must be (V, 3), got {tuple(verts.shape)}")
-    if verts.device != dev:
-        raise ValueError(f"mesh_topology.{name}: verts on {verts.device}, faces on {dev}")
-    return verts.detach().contiguous()
-
-
 def topology_report(verts, faces):
     """{"verts", "faces": the sizes given; "verts_used", "faces_valid", "edges", "boundary_edges", "nonmanifold_edges",
     "misoriented_edges"; "components": those of mesh_clean.connected_components that have a used vertex (faces with an index out of
@@ -114,15 +90,12 @@ def topology_report(verts, faces):
     faces_valid > 0; "genus" = components - euler / 2 when watertight, else None; "edge_length": {"min", "mean", "max"} over the
     edges, fp32 torch ops on the device, None each without an edge}."""
     from . import mesh_clean
-    if not torch.is_tensor(faces) or not faces.is_cuda:
-        raise RuntimeError("mesh_topology.topology_report needs CUDA/HIP tensors (dg-mesh_amd has no CPU path)")
-    verts = _verts("topology_report", verts, faces.device)
+    verts, faces = mesh_args.mesh("mesh_topology.topology_report", verts, faces)
     V = int(verts.shape[0])
     table = EdgeTable("topology_report", faces, V)
     info = table.info
     rep = {"verts": V, "faces": table.F}
     rep.update({k: info[k] for k in ("verts_used", "faces_valid", "edges", "boundary_edges", "nonmanifold_edges", "misoriented_edges")})
-    faces = faces.detach()
     inside = ((faces >= 0) & (faces < V)).all(dim=1)
     rep["components"] = 0
     if rep["faces_valid"] > 0:

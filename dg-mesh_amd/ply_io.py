@@ -204,6 +204,18 @@ def read_mesh_ply(path, return_colors=False):
     return verts, faces, colors
 
 
+def read_mesh_ply_on_device(path, device):
+    """read_mesh_ply for the command lines of the mesh tools: verts (V, 3) float32, faces (F, 3) int32 and colours (V, 3) float32,
+    tensors on `device`; colours None when the file has none.  The byte k is read as (k + 0.5) / 255: write_mesh_ply and the
+    texture writers quantise floats in [0, 1] as clip(c * 255) truncated, which gives k back for every byte k, so a tool that does
+    not touch a colour writes the byte it read."""
+    import torch
+    verts, faces, colors = read_mesh_ply(path, return_colors=True)
+    if colors is not None:
+        colors = torch.from_numpy((colors[:, :3].astype(np.float32) + np.float32(0.5)) / np.float32(255.0)).to(device)
+    return torch.from_numpy(verts).to(device), torch.from_numpy(faces).to(device), colors
+
+
 # ---- point clouds with normals (pointcloud_init.ply of normal_initialization, R/scene/gaussian_model_dpsr_dynamic_anchor.py:722-729) --
 def write_pointcloud_ply(path, points, normals):
     """points (N, 3), normals (N, 3) (numpy arrays or tensors on any device) as `element vertex N` with float x y z nx ny nz,

@@ -227,12 +227,9 @@ class MeshPhase:
     def extract_mesh(self, g, deform=None, deform_normal=None, t=None, clean=None, simplify=None, smooth=None, repair=None):
         """export_mesh (R/scene/gaussian_model_dpsr_dynamic_anchor.py:831-856): world-space (verts, faces) of the surface at time t.
         deform / deform_normal: DeformModel-like objects with .step(xyz, t) (the first output is used), or None for the canonical
-        Gaussians; t: a scalar time (float or tensor).  clean: None, or a mesh_clean.CleanSpec (or a dict of its fields): the
-        components that fail it are removed (mesh_clean.clean_mesh).  simplify: None, or a mesh_simplify.SimplifySpec (or a dict of its
-        fields): the mesh is then decimated by quadric vertex clustering (mesh_simplify.simplify_mesh), after `clean`.  smooth: None, or a
-        mesh_smooth.SmoothSpec (or a dict of its fields): the mesh is smoothed (mesh_smooth.smooth_mesh) after `clean` and BEFORE
-        `simplify` -- denoised first, decimated after.  repair: None, or a mesh_repair.RepairSpec (or a dict of its fields): the mesh
-        is repaired (mesh_repair.repair_mesh: every body oriented consistently and outwards, small holes filled) LAST, after `simplify`.
+        Gaussians; t: a scalar time (float or tensor).  The four stages of mesh_post, each None or its spec (or a dict of its
+        fields) -- clean: a mesh_clean.CleanSpec, first.  simplify: a mesh_simplify.SimplifySpec, after `clean`.  smooth: a
+        mesh_smooth.SmoothSpec, after `clean` and BEFORE `simplify`.  repair: a mesh_repair.RepairSpec, LAST, after `simplify`.
         Never applied inside the training step.  Write the result with ply_io.write_mesh_ply."""
         if self.dpsr is None:
             raise RuntimeError("MeshPhase.extract_mesh needs the DPSR module")
@@ -243,19 +240,8 @@ class MeshPhase:
         if isinstance(d_normal, (tuple, list)):
             d_normal = d_normal[0]
         verts, faces = self.surface(g, self.psr(g, d_xyz, d_normal))
-        if clean is not None:
-            from . import mesh_clean
-            verts, faces = mesh_clean.apply(clean, verts, faces)
-        if smooth is not None:
-            from . import mesh_smooth
-            verts, faces = mesh_smooth.apply(smooth, verts, faces)
-        if simplify is not None:
-            from . import mesh_simplify
-            verts, faces = mesh_simplify.apply(simplify, verts, faces)
-        if repair is not None:
-            from . import mesh_repair
-            verts, faces = mesh_repair.apply(repair, verts, faces)
-        return verts, faces
+        from . import mesh_post
+        return mesh_post.apply(verts, faces, clean=clean, smooth=smooth, simplify=simplify, repair=repair)
 
 
 class Trainer:

@@ -385,19 +385,15 @@ def export_dynamic_mesh(gaussians, deform, deform_back, mesh, out_dir, frames=20
     """The dynamic-mesh sequence of R/train.py:389-423: dynamic_mesh/frame_{i}.ply under out_dir for t = i / frames, i < frames,
     with vertex colours (ply_io.write_mesh_ply).  Colours are written as clamp(c, 0, 1) * 255 truncated, as testing() writes them;
     the reference's astype(np.uint8) of the unscaled [0, 1] colours at this place is a bug (every channel becomes 0 or 1).
-    clean: None, or a mesh_clean.CleanSpec (or a dict of its fields): each written mesh loses the components that fail it
-    (mesh_clean.clean_mesh; the colours follow their vertices).  simplify: None, or a mesh_simplify.SimplifySpec (or a dict of its
-    fields): each written mesh is then decimated by quadric vertex clustering, after `clean`; a new vertex takes the colour of its
-    cluster's representative.  smooth: None, or a mesh_smooth.SmoothSpec (or a dict of its fields): each written mesh is smoothed
-    (Taubin or Laplacian, mesh_smooth.smooth_mesh) after `clean` and BEFORE `simplify` -- denoised first, decimated after; faces and
-    colours are untouched by it.  repair: None, or a mesh_repair.RepairSpec (or a dict of its fields): each written mesh is repaired
-    (mesh_repair.repair_mesh: every body oriented consistently and outwards, small holes filled) LAST, after `simplify` -- vertex
-    clustering is what opens and misorients a mesh; a new vertex takes the mean colour of its rim.  texture: None, or a mesh_texture.TextureSpec (or a dict of its fields): every frame ALSO gets
-    dynamic_mesh_textured/frame_{i}.obj (+ .mtl, .png) or .glb, the written mesh with a texture atlas baked after `clean` / `smooth` /
-    `simplify` / `repair` from the appearance network itself (mesh_texture.bake with appearance_color_fn at the frame's time), not from the
+    The four stages of mesh_post, each None or its spec (or a dict of its fields), change each written mesh, its colours following
+    their vertices (mesh_post) -- clean: a mesh_clean.CleanSpec, first.  simplify: a mesh_simplify.SimplifySpec, after `clean`.
+    smooth: a mesh_smooth.SmoothSpec, after `clean` and BEFORE `simplify`.  repair: a mesh_repair.RepairSpec, LAST, after
+    `simplify`.  texture: None, or a
+    mesh_texture.TextureSpec (or a dict of its fields): every frame ALSO gets dynamic_mesh_textured/frame_{i}.obj (+ .mtl, .png) or
+    .glb, the written mesh with a texture atlas baked after mesh_post from the appearance network itself (mesh_texture.bake with appearance_color_fn at the frame's time), not from the
     decimated vertex colours; with ao_samples > 0 the texture is multiplied by the baked ambient occlusion
     (mesh_texture.bake_ambient_occlusion); the PLY files are what they are without it.  -> the list of the PLY paths."""
-    from . import mesh_clean, mesh_repair, mesh_simplify, mesh_smooth, mesh_texture
+    from . import mesh_post, mesh_texture
     from .evaluate import mesh_and_colors
     from .ply_io import write_mesh_ply
     who = "export_dynamic_mesh"
@@ -414,10 +410,8 @@ def export_dynamic_mesh(gaussians, deform, deform_back, mesh, out_dir, frames=20
     for i in range(n):
         fid = torch.tensor([i / n], dtype=torch.float32, device=dev)
         _, d_xyz, d_normal = _deformations(gaussians, deform, deform_normal, fid)
-        verts, faces, vtx_color = mesh_clean.apply(clean, *mesh_and_colors(mesh, gaussians, deform_back, d_xyz, d_normal, fid, who=who))
-        verts, faces, vtx_color = mesh_smooth.apply(smooth, verts, faces, vtx_color)
-        verts, faces, vtx_color = mesh_simplify.apply(simplify, verts, faces, vtx_color)
-        verts, faces, vtx_color = mesh_repair.apply(repair, verts, faces, vtx_color)
+        verts, faces, vtx_color = mesh_post.apply(*mesh_and_colors(mesh, gaussians, deform_back, d_xyz, d_normal, fid, who=who),
+                                                  clean=clean, smooth=smooth, simplify=simplify, repair=repair)
         paths.append(os.path.join(out_dir, "dynamic_mesh", f"frame_{i}.ply"))
         write_mesh_ply(paths[-1], verts, faces, vertex_colors=vtx_color)
         if tex_spec is not None:

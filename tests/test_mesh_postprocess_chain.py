@@ -435,6 +435,108 @@ def test_export_dynamic_mesh_with_every_option(scene, tmp_path):  # noqa: F811
         {n: open(tmp_path / "again" / "dynamic_mesh_textured" / n, "rb").read() for n in os.listdir(folder)}
 
 
+# ---- mesh_post.apply is the four calls, and the other three exports make it ---------------------------------------------------------------
+def by_hand(mesh, clean=None, smooth=None, simplify=None, repair=None):
+    """The four apply calls in the documented order, spelt out."""
+    mesh = pkg("mesh_clean").apply(clean, *mesh)
+    mesh = pkg("mesh_smooth").apply(smooth, *mesh)
+    mesh = pkg("mesh_simplify").apply(simplify, *mesh)
+    return pkg("mesh_repair").apply(repair, *mesh)
+
+
+@pytest.mark.parametrize("which", ["all", "clean", "smooth", "simplify", "repair", "none"])
+def test_mesh_post_is_the_four_calls_by_hand(which):
+    """mesh_post.apply on the marching-cubes mesh with a colour per vertex: vertices, faces and colours byte for byte those of the
+    four calls, with every stage on (simplify at grid16), with each stage alone and with none."""
+    mv, mf = device_head()[1]
+    assert (len(mv), len(mf)) == (2196, 4330)
+    colour = np.random.default_rng(17).random((len(mv), 3)).astype(np.float32)
+    specs = {"clean": C.CLEAN, "smooth": C.SMOOTH, "simplify": C.CASES["grid16"], "repair": {}}
+    on = specs if which == "all" else {k: v for k, v in specs.items() if k == which}
+    mesh = (dev(mv), dev(mf), dev(colour))
+    got = pkg("mesh_post").apply(*mesh, **on)
+    want = by_hand(mesh, **on)
+    assert len(got) == len(want) == 3
+    for g, w, name in zip(got, want, ("vertices", "faces", "colours")):
+        same(host(g), host(w), f"{which}: {name}")
+    print(f"{which}: V {len(mv)} F {len(mf)} -> V {got[0].shape[0]} F {got[1].shape[0]}")
+    if which == "none":
+        assert all(g is m for g, m in zip(got, mesh))
+    else:
+        assert any(g.shape != m.shape or not torch.equal(g, m) for g, m in zip(got, mesh))  # the stage did something
+
+
+EXPORT_SPECS = dict(clean=C.CLEAN, smooth={"iterations": 3}, simplify={"grid": 12}, repair={})
+
+
+def replay(mesh, fields):
+    """mesh.psr hands out the recorded fields again, in call order (DPSR's splat sums with float atomics)."""
+    left = iter(fields)
+    mesh.psr = lambda *a, **k: next(left)
+
+
+def test_extract_mesh_with_every_option(scene):  # noqa: F811
+    g, m = scene["g"], scene["mesh"]
+    fields, orig = _record_psr(m)
+    try:
+        plain = m.extract_mesh(g, scene["deform"], m.deform_normal, t=0.0)
+        replay(m, fields)
+        full = m.extract_mesh(g, scene["deform"], m.deform_normal, t=0.0, **EXPORT_SPECS)
+    finally:
+        m.psr = orig
+    want = by_hand(plain, **EXPORT_SPECS)
+    assert len(full) == 2 and full[1].shape[0] < plain[1].shape[0]
+    same(host(full[0]), host(want[0]), "vertices")
+    same(host(full[1]), host(want[1]), "faces")
+
+
+def test_testing_writes_the_mesh_with_every_option(scene, tmp_path):  # noqa: F811
+    EV, io, SC = pkg("evaluate"), pkg("ply_io"), pkg("scene")
+    g, m, cam = scene["g"], scene["mesh"], scene["cameras"][0]
+    kw = dict(pipe=SC.PipelineParams(), background=torch.ones(3, device=DEV), mesh=m, save_meshes=True)
+    fields, orig = _record_psr(m)
+    try:
+        EV.testing(g, scene["deform"], scene["deform_back"], [cam], out_dir=str(tmp_path / "plain"), **kw)
+        replay(m, fields)
+        EV.testing(g, scene["deform"], scene["deform_back"], [cam], out_dir=str(tmp_path / "full"), **EXPORT_SPECS, **kw)
+        replay(m, fields)
+        with torch.no_grad():
+            mesh = EV.mesh_and_colors(m, g, scene["deform_back"], None, None, cam.fid)
+    finally:
+        m.psr = orig
+    written = lambda name: open(tmp_path / name / "test_results" / "dynamic_mesh" / "frame_0.ply", "rb").read()
+    io.write_mesh_ply(str(tmp_path / "replayed.ply"), *mesh[:2], vertex_colors=mesh[2])
+    assert written("plain") == open(tmp_path / "replayed.ply", "rb").read()  # the mesh the plain run wrote
+    mesh = by_hand(mesh, **EXPORT_SPECS)
+    io.write_mesh_ply(str(tmp_path / "by_hand.ply"), *mesh[:2], vertex_colors=mesh[2])
+    assert written("full") == open(tmp_path / "by_hand.ply", "rb").read() and written("full") != written("plain")
+
+
+def test_export_correspondence_with_every_option(scene, tmp_path):  # noqa: F811
+    """mode "canonical": a frame's colours are the palette of its own vertices' canonical positions, which the test forms itself."""
+    CO, io = pkg("correspondence"), pkg("ply_io")
+    g, m = scene["g"], scene["mesh"]
+    args = (g, scene["deform"], scene["deform_back"], m)
+    fields, orig = _record_psr(m)
+    try:
+        plain = CO.export_correspondence(*args, str(tmp_path / "plain"), frames=1, mode="canonical", n_tracks=64)["paths"][0]
+        assert len(fields) == 2  # mesh(t_ref), then the frame's
+        replay(m, fields)
+        full = CO.export_correspondence(*args, str(tmp_path / "full"), frames=1, mode="canonical", n_tracks=64, **EXPORT_SPECS)["paths"][0]
+    finally:
+        m.psr = orig
+    fid = torch.zeros(1, device=DEV)
+    with torch.no_grad():
+        verts, faces = (t.contiguous() for t in m.surface(g, fields[1]))
+        colour = CO.palette(CO.to_canonical(verts, fid, scene["deform_back"]), g.gaussian_center, g.gaussian_scale, "checker", 8)
+    io.write_mesh_ply(str(tmp_path / "replayed.ply"), verts, faces, vertex_colors=colour)
+    assert open(plain, "rb").read() == open(tmp_path / "replayed.ply", "rb").read()  # the mesh the plain export wrote
+    mesh = by_hand((verts, faces, colour), **EXPORT_SPECS)
+    io.write_mesh_ply(str(tmp_path / "by_hand.ply"), *mesh[:2], vertex_colors=mesh[2])
+    written = open(full, "rb").read()
+    assert written == open(tmp_path / "by_hand.ply", "rb").read() and written != open(plain, "rb").read()
+
+
 # ---- the chain between guard zones --------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", CASES)
 def test_chain_between_guard_zones(case):
