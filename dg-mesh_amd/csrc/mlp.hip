@@ -25,6 +25,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <utility>
+
 #include "dgm_host.hpp"
 #include "mlp_planes.hpp"
 #include "mlp_planes5.hpp"
@@ -651,7 +653,7 @@ struct Ws {
     unsigned* matmax;
     uint4 *Wh4f, *Wh4b;
     float *wsc_hf, *wsc_hb;
-    float *bias_s[8];           // round 6: biases times their layer's column scales (mlp_prep4c_kernel)
+    float *bias_s[8];           // round 6: biases times their layer's column scales (prep4c_block)
     unsigned* tickets;          // eight counters: the reduce role of the grouped paired launches (pair_reduce_role), cleared by every grouped pass
     float *beff[2], *temb_row;  // round 6: the call's time row, kept for the backward pass (beff: the folded biases of the first version, unused -- they are formed where the biases are pre-scaled)
     size_t bytes;
@@ -668,6 +670,52 @@ int num_cus() {
     }
     return cache[slot];
 }
+// ---- environment switches of the MLP: all of them, read once when the library is loaded -------------------------------------------
+//   DGM_MLP_GEMM=f16x3p|f16x3p8|f16x3p5|f32  initial arithmetic mode (3 | 4 | 5 | 1, see g_gemm_mode; dgm_mlp_set_gemm changes it)
+//   DGM_MLP_REDUCE_IN_PAIR=<n>                 initial g_reduce_in_pair (dgm_mlp_set_reduce_in_pair changes it); default P4_REDUCE_IN_PAIR = 0
+//   DGM_MLP_PAIR=<n>                           weight-gradient workgroups of a paired backward launch (bwd_plan), 0 = two separate launches;
+//                                              default: a fixed share of the CUs, chosen by measurement at N = 100 k
+//   DGM_P4_EXPS_LIMIT=<n>                      tiles per workgroup whose exponents the layer GEMM keeps in its LDS table (1 .. 512 = default: N <= 4 M
+//                                              rows on 256 CUs; the rest are read from HBM as they come): lets a test reach the second path at an ordinary batch size
+//   DGM_MLP_HEADS_FUSED=0                      the heads in a launch of their own instead of inside layer 7's (forward_folded; A/B runs)
+//   DGM_P4_XCD_OFF                             (-DP4_XCD_REDUCE variant builds only) dgm_p4_probe's paired launch without the per-XCD pre-reduction
+// Three finished A/B switches went with the branches only they reached; their results stay where the kept code is: DGM_MLP_EMBED_MERGED
+// (forward_folded), DGM_P4_G7_MULT (backward_planes), DGM_MLP_PAIR_CHUNKED (bwd_plan).
+#ifndef P4_REDUCE_IN_PAIR
+#define P4_REDUCE_IN_PAIR 0
+#endif
+struct MlpEnv {
+    int gemm_mode, reduce_in_pair, pair, exps_limit;
+    bool heads_fused;
+#ifdef P4_XCD_REDUCE
+    bool xcd_off;
+#endif
+};
+const MlpEnv g_env = [] {
+    auto num = [](const char* name, int dflt) {
+        const char* e = getenv(name);
+        return e ? atoi(e) : dflt;
+    };
+    MlpEnv v;
+    v.gemm_mode = 3;
+    if (const char* e = getenv("DGM_MLP_GEMM")) {
+        if (strcmp(e, "f32") == 0) v.gemm_mode = 1;
+        else if (strcmp(e, "f16x3p8") == 0) v.gemm_mode = 4;
+        else if (strcmp(e, "f16x3p5") == 0) v.gemm_mode = 5;
+        else if (strcmp(e, "f16x3p") != 0)
+            fprintf(stderr, "libdgmesh_hip: unknown DGM_MLP_GEMM=\"%s\" (f16x3p | f16x3p8 | f16x3p5 | f32): using f16x3p\n", e);
+    }
+    v.reduce_in_pair = num("DGM_MLP_REDUCE_IN_PAIR", P4_REDUCE_IN_PAIR);
+    if (v.reduce_in_pair < 0) v.reduce_in_pair = 0;
+    v.pair = num("DGM_MLP_PAIR", -1);
+    v.exps_limit = num("DGM_P4_EXPS_LIMIT", 512);
+    v.exps_limit = v.exps_limit < 1 ? 1 : (v.exps_limit > 512 ? 512 : v.exps_limit);
+    v.heads_fused = num("DGM_MLP_HEADS_FUSED", 1) != 0;
+#ifdef P4_XCD_REDUCE
+    v.xcd_off = getenv("DGM_P4_XCD_OFF") != nullptr;
+#endif
+    return v;
+}();
 // 3: f16x3p (default; mlp_planes.hpp): power-of-two scaled operands split into 2 binary16, 3 partial products on the f16 matrix
 //    cores, on plane-format activations -- split once by the producer, one exponent per 32-row tile.
 // 4: the same arithmetic on round 3-5's kernel forms ("f16x3p8": eight waves x 32 columns per layer GEMM, the skip layer's
@@ -676,30 +724,15 @@ int num_cus() {
 // 5: mode 3 with EVERY 256-wide layer GEMM in the one-wave-per-SIMD form ("f16x3p5": mlp_gemm5_kernel<0, 0> forward, <0, 1> in
 //    unpaired backward passes).  Measured slower than the eight-wave form (50.5 vs 48.9 us under the power probe, 54.5
 //    vs 48.4 inside a network pass), so mode 3 uses that form for the K = 320 skip layer only; kept selectable for the record.
-// 1: native fp32 MFMA (v_mfma_f32_32x32x2_f32).  Initial value from DGM_MLP_GEMM=f16x3p|f16x3p8|f16x3p5|f32.
+// 1: native fp32 MFMA (v_mfma_f32_32x32x2_f32).
 // (0 = "bf16x6 for every GEMM" was retired in round 4, 2 = "f16x3" on fp32 rows in round 5: both are ignored by dgm_mlp_set_gemm.)
-int g_gemm_mode = [] {
-    const char* e = getenv("DGM_MLP_GEMM");
-    if (e == nullptr) return 3;
-    if (strcmp(e, "f32") == 0) return 1;
-    if (strcmp(e, "f16x3p8") == 0) return 4;
-    if (strcmp(e, "f16x3p5") == 0) return 5;
-    if (strcmp(e, "f16x3p") != 0) fprintf(stderr, "libdgmesh_hip: unknown DGM_MLP_GEMM=\"%s\" (f16x3p | f16x3p8 | f32): using f16x3p\n", e);
-    return 3;
-}();
+int g_gemm_mode = g_env.gemm_mode;
 // Pieces per K = 256 reduction job that a grouped backward pass reduces inside the NEXT layer's paired launch (pair_reduce_role,
 // mlp_planes.hpp) instead of in the final mlp_reduce_dw_all_kernel launch: 0 = none (the launches of before), values above a job's
-// piece count mean all of it.  dgm_mlp_set_reduce_in_pair() / DGM_MLP_REDUCE_IN_PAIR=<n>; the gradients do not depend on it.
+// piece count mean all of it.  The gradients do not depend on it.
 // Off by default: at the full cap the kernels of a step take 59 us less, but the bench's gain of 1.2-1.8 % is smaller
 // than its run-to-run spread on one box (profiles/reduce_in_pair_bench_ab.json), and a gain that cannot be told from noise is not one.
-#ifndef P4_REDUCE_IN_PAIR
-#define P4_REDUCE_IN_PAIR 0
-#endif
-int g_reduce_in_pair = [] {
-    const char* e = getenv("DGM_MLP_REDUCE_IN_PAIR");
-    const int n = e ? atoi(e) : P4_REDUCE_IN_PAIR;
-    return n < 0 ? 0 : n;
-}();
+int g_reduce_in_pair = g_env.reduce_in_pair;
 // arithmetic the last forward pass on a workspace ran in: the backward pass must match (its scales and masks were produced by
 // that forward pass).  A small host-side table keyed by the workspace pointer; an unknown workspace is not checked.
 struct WsMode {
@@ -816,38 +849,27 @@ int check_params(const dgm_mlp_params* p) {
 }
 
 // ---- plane path (mlp_planes.hpp) -----------------------------------------------------------------------------------------
-template <typename K>
-hipError_t p4_lds_attr(K kernel, int bytes, bool* done) {  // dynamic LDS above 48 KB needs the attribute once per device
-    if (*done) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) *done = true;
-    return e;
+// Every launch with dynamic LDS: above 48 KB the kernel's limit has to be raised first, once per kernel (= per instantiation of
+// this template) and device.  Returns 0, or 1 with the reason in dgm_last_error().
+template <auto Kernel, typename... Args>
+int launch_lds(dim3 grid, dim3 block, int lds, hipStream_t st, const Args&... args) {
+    static int raised[DGM_MAX_DEVICES] = {0};  // bytes the kernel's limit stands at on each device
+    int& have = raised[current_device_slot()];
+    if (lds > have) {
+        if (hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+            return fail("mlp: cannot raise the dynamic LDS limit of a plane-path kernel");
+        have = lds;
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+    return 0;
 }
-#define P4_LAUNCH(kernel_, cfg_lds_, grid_, st_, args_)                                                                \
-    {                                                                                                                  \
-        static bool done_[DGM_MAX_DEVICES] = {false};                                                                  \
-        if (p4_lds_attr(kernel_, cfg_lds_, &done_[current_device_slot()]) != hipSuccess)                               \
-            return fail("mlp: cannot raise the LDS limit of a plane-path kernel");                                 \
-        hipLaunchKernelGGL(kernel_, dim3(grid_), dim3(512), cfg_lds_, st_, args_);                                     \
-    }
-#define P5_LAUNCH(kernel_, cfg_lds_, grid_, st_, args_)                                                                \
-    {                                                                                                                  \
-        static bool done_[DGM_MAX_DEVICES] = {false};                                                                  \
-        if (p4_lds_attr(kernel_, cfg_lds_, &done_[current_device_slot()]) != hipSuccess)                               \
-            return fail("mlp: cannot raise the LDS limit of a plane-path kernel");                                 \
-        hipLaunchKernelGGL(kernel_, dim3(grid_), dim3(256), cfg_lds_, st_, args_);                                     \
-    }
 typedef Gemm4Cfg<16, 1024, 512, 0, false, 8> CfgFwd;
 typedef Gemm4Cfg<16, 1024, 512, 2, false, 8> CfgSkip;
 typedef Gemm4Cfg<16, 1024, 512, 1, false, 8> CfgBwd;
 typedef Gemm4Cfg<6, 384, 192, 0, true, 8> CfgL0;
-typedef Gemm4Cfg<16, 1024, 512, 3, false, 1> CfgHeads;
-typedef Gemm4Cfg<1, 128, 64, 1, false, 8> CfgG7;
 typedef Gemm4Cfg<4, 256, 128, 0, false, 8, true> CfgL0F;   // layer 0 on the 64-column embedding
 typedef Gemm4Cfg<16, 1024, 512, 0, false, 8, true> CfgFwdC;   // round 6's forms: one weight scale per output column
 typedef Gemm4Cfg<16, 1024, 512, 1, false, 8, true> CfgBwdC;
-typedef Gemm4Cfg<16, 1024, 512, 3, false, 1, true> CfgHeadsC;
-typedef Gemm4Cfg<1, 128, 64, 1, false, 8, true> CfgG7C;
 typedef Gemm5Cfg<0, 0> Cfg5Fwd;
 typedef Gemm5Cfg<0, 1> Cfg5Bwd;
 typedef Gemm5Cfg<4, 0> Cfg5Skip;
@@ -860,235 +882,283 @@ typedef Dw4Cfg<8, 1, 1024, 512, 128, 64> CfgDwH;
 #define P4_PAIR_SHARE_NUM 128  // share of the CUs on the weight gradient in a paired backward launch: NUM / DEN (measured at N = 100 k: 96 -> 1.50, 112 -> 1.43, 128 -> 1.41, 144 -> 1.43, off -> 1.56 ms per network pass)
 #define P4_PAIR_SHARE_DEN 256
 #endif
+// the paired launches' dynamic LDS: either role's (the larger form's, for both forms)
+constexpr int LDS_PAIR = CfgBwdC::LDS > CfgDw::LDS ? CfgBwdC::LDS : CfgDw::LDS;
 
-// Tiles per workgroup whose exponents the layer GEMM keeps in its LDS table (512: N <= 4 M rows on 256 CUs; the rest are read from
-// HBM as they come).  DGM_P4_EXPS_LIMIT=<n> lowers it so that a test reaches the second path at an ordinary batch size.
-int p4_exps_limit() {
-    static int v = [] {
-        const char* e = getenv("DGM_P4_EXPS_LIMIT");
-        const int n = e ? atoi(e) : 512;
-        return n < 1 ? 1 : (n > 512 ? 512 : n);
-    }();
-    return v;
-}
-
-// workgroups of a backward launch that run the weight gradient (mlp_bwd_pair_kernel); 0 = two separate launches.
-// DGM_MLP_PAIR=<n> overrides (0 disables); default: a fixed share of the CUs, chosen by measurement at N = 100 k.
-int p4_pair_split(int ntiles, int gx) {
-    static int env = [] {
-        const char* e = getenv("DGM_MLP_PAIR");
-        return e ? atoi(e) : -1;
-    }();
-    if (gx < 64 || ntiles < 4 * gx) return 0;  // small problems: nothing to balance
-    int n = env >= 0 ? env : (gx * P4_PAIR_SHARE_NUM) / P4_PAIR_SHARE_DEN;
-    if (n >= gx) n = gx - 1;
-    return n;
-}
-
-// fold: one time value per call (temb_stride == 0) on round 6's kernel forms -- the embedding is 64 columns wide, the time row sits
-// in the biases of layer 0 and the skip layer, the skip layer is one K = 320 GEMM (no `Cin`), the 256-wide layers run one wave per SIMD.
-int forward_planes(const dgm_mlp_params* p, int N, const float* x, const float* temb, int temb_stride, const Ws& w, float* out,
-                   hipStream_t st, const bool fold, const bool all5, const float* xadd = nullptr, const int xadd_stride = 0) {
-    const P4Plan pl = p4_plan(N);
-    const int nt = pl.ntiles, gx = nt < num_cus() ? nt : num_cus();
-    const int sk = p->skip_layer;
-    const int EW = fold ? 64 : MLP_EMB;
-    // the heads inside layer 7's launch (mlp_gemm5_kernel<0, 2>) instead of a launch of their own that reads Y_7 again: 64 us against
-    // 50 + 26, +0.95 % on the bench (308.8 / 309.4 / 309.3 against 306.0 / 306.1 / 306.5 it/s, interleaved on one box);
-    // DGM_MLP_HEADS_FUSED=0 restores the separate launch (A/B runs)
-    static const bool heads_env = [] { const char* e = getenv("DGM_MLP_HEADS_FUSED"); return !(e && atoi(e) == 0); }();
-    const bool heads_fused = fold && heads_env && p->n_out <= 16;
-    // embedding planes + the maxima of the nine weight tensors (W_0 .. W_7, Wh)
-    AbsMaxBatch am;
-    am.n_jobs = fold ? 0 : 9;  // (round 6's forms scale per output column: mlp_prep4c_kernel takes its columns' maxima itself)
-    for (int l = 0; l < 8; l++) am.job[l].W = p->W[l], am.job[l].n = MLP_W * layer_in(p, l);
-    am.job[8].W = p->Wh, am.job[8].n = p->n_out * MLP_W;
-    if (!fold)
-        hipLaunchKernelGGL(mlp_embed4_kernel, dim3(nt + 8 * am.n_jobs), dim3(256), 0, st, N, nt, x, temb, temb_stride, p->t_dim,
-                           (unsigned char*)w.emb, w.Eexp, am, w.matmax, EW, xadd, xadd_stride);
-    if (fold) {  // every weight matrix as two binary16 planes, one power-of-two scale per OUTPUT COLUMN, biases pre-scaled
-        Prep4cBatch pc;
-        int nc = 0;
-        pc.temb = temb, pc.temb_row = w.temb_row, pc.T = p->t_dim;
-        auto addc = [&](int mode, int Kp, int ncols, int in_features, int hoff, int k_valid, int col_valid, const float* Wp, uint4* Bp,
-                        float* inv_scale, const float* bias_in, float* bias_out, int fold_time = 0) {
-            Prep4cJob& q = pc.job[nc++];
-            q.fold = fold_time;
-            q.j.mode = mode, q.j.Kp = Kp, q.j.ncols = ncols, q.j.in_features = in_features, q.j.emb_dim = p->emb_dim, q.j.hoff = hoff;
-            q.j.k_valid = k_valid, q.j.col_valid = col_valid, q.j.W = Wp, q.j.Bp = Bp, q.j.inv_scale = inv_scale;
-            q.bias_in = bias_in, q.bias_out = bias_out;
-        };
-        for (int l = 0; l < 8; l++) {
-            const int Kp = l == 0 ? 64 : (l == sk ? 320 : MLP_W);
-            addc(0, Kp, MLP_W, layer_in(p, l), 0, MLP_W, MLP_W, p->W[l], w.Wt3[l], w.wsc_f[l], p->b[l], w.bias_s[l], (l == 0 || l == sk) ? 1 : 0);
-            if (l >= 1) addc(1, MLP_W, MLP_W, layer_in(p, l), l == sk ? p->emb_dim : 0, MLP_W, MLP_W, p->W[l], w.Wd3[l], w.wsc_d[l], nullptr, nullptr);
-        }
-        addc(0, MLP_W, 32, MLP_W, 0, MLP_W, p->n_out, p->Wh, w.Wh4f, w.wsc_hf, nullptr, nullptr);   // heads forward: B[k][o] = Wh[o][k]
-        addc(1, 16, MLP_W, MLP_W, 0, p->n_out, MLP_W, p->Wh, w.Wh4b, w.wsc_hb, nullptr, nullptr);    // heads backward: B[o][c] = Wh[o][c]
-        // ... in ONE launch with the embedding planes (DGM_MLP_EMBED_MERGED=0: two launches, for A/B runs)
-        static const bool merged = [] { const char* e = getenv("DGM_MLP_EMBED_MERGED"); return !(e && atoi(e) == 0); }();
-        if (merged) {
-            const int n_prep = (MLP_W / P4C_COLS) * nc;
-            hipLaunchKernelGGL(mlp_embed4c_kernel, dim3(n_prep + nt), dim3(256), 0, st, N, x, (unsigned char*)w.emb, w.Eexp, EW, pc, n_prep, xadd, xadd_stride);
-        } else {
-            hipLaunchKernelGGL(mlp_embed4_kernel, dim3(nt), dim3(256), 0, st, N, nt, x, temb, temb_stride, p->t_dim,
-                               (unsigned char*)w.emb, w.Eexp, am, w.matmax, EW, xadd, xadd_stride);
-            hipLaunchKernelGGL(mlp_prep4c_kernel, dim3(MLP_W / P4C_COLS, nc), dim3(256), 0, st, pc);
-        }
-    }
-    // (rounds 3-5's forms: one power-of-two scale per matrix)
-    Prep4Batch pb;
-    int nj = 0;
-    auto add = [&](int mode, int Kp, int ncols, int in_features, int hoff, int k_valid, int col_valid, const float* Wp, uint4* Bp,
-                   float* inv_scale, int mat) {
-        Prep4Job& q = pb.job[nj++];
-        q.j.mode = mode, q.j.Kp = Kp, q.j.ncols = ncols, q.j.in_features = in_features, q.j.emb_dim = p->emb_dim, q.j.hoff = hoff;
-        q.j.k_valid = k_valid, q.j.col_valid = col_valid, q.j.W = Wp, q.j.Bp = Bp, q.j.inv_scale = inv_scale, q.mat = mat;
-    };
-    for (int l = 0; l < 8; l++) {
-        if (fold && l == 0) add(0, 64, MLP_W, layer_in(p, l), 0, MLP_W, MLP_W, p->W[l], w.Wt3[l], w.wsc_f[l], l);
-        else if (fold && l == sk) add(0, 320, MLP_W, layer_in(p, l), 0, MLP_W, MLP_W, p->W[l], w.Wt3[l], w.wsc_f[l], l);
-        else if (l == sk) {  // K = 352 = embedding half (rides along with layer 0) | trunk half
-            add(0, MLP_EMB, MLP_W, layer_in(p, l), 0, MLP_W, MLP_W, p->W[l], w.Wt3[l], w.wsc_e, l);
-            add(0, MLP_W, MLP_W, layer_in(p, l), p->emb_dim, MLP_W, MLP_W, p->W[l], w.Wt3[l] + (size_t)MLP_EMB * MLP_W / 4, w.wsc_f[l], l);
-        } else
-            add(0, layer_kp(p, l), MLP_W, layer_in(p, l), 0, MLP_W, MLP_W, p->W[l], w.Wt3[l], w.wsc_f[l], l);
-        if (l >= 1) add(1, MLP_W, MLP_W, layer_in(p, l), l == sk ? p->emb_dim : 0, MLP_W, MLP_W, p->W[l], w.Wd3[l], w.wsc_d[l], l);
-    }
-    add(0, MLP_W, 32, MLP_W, 0, MLP_W, p->n_out, p->Wh, w.Wh4f, w.wsc_hf, 8);   // heads forward: B[k][o] = Wh[o][k]
-    add(1, 16, MLP_W, MLP_W, 0, p->n_out, MLP_W, p->Wh, w.Wh4b, w.wsc_hb, 8);    // heads backward: B[o][c] = Wh[o][c]
-    if (!fold) hipLaunchKernelGGL(mlp_prep4_kernel, dim3(8, nj), dim3(256), 0, st, pb, w.matmax);
-
+Gemm4Args gemm4_args(int N, int nt) {
     Gemm4Args a;
     memset(&a, 0, sizeof(a));
-    a.ntiles = nt, a.M = N, a.exps_limit = p4_exps_limit();
-    if (fold) {
-        // layer 0: K = 64, eight waves (HBM-bound: 26 MB in, 102 MB of planes out)
-        a.A = (const unsigned char*)w.emb, a.Aexp = w.Eexp, a.Bp = w.Wt3[0], a.b_inv = w.wsc_f[0], a.bias = w.bias_s[0];
-        a.mask_out = w.mask[0], a.C = (unsigned char*)w.Y[0], a.Cexp = w.Yexp[0];
-        P4_LAUNCH((mlp_gemm4_kernel<4, 256, 128, 0, false, 8, true>), CfgL0F::LDS, gx, st, a)
-        Gemm5Args b;
-        memset(&b, 0, sizeof(b));
-        b.ntiles = nt, b.M = N, b.exps_limit = p4_exps_limit();
-        for (int l = 1; l < 8; l++) {
-            b.A = (const unsigned char*)w.Y[l - 1], b.Aexp = w.Yexp[l - 1], b.Bp = w.Wt3[l], b.b_inv = w.wsc_f[l];
-            b.mask_out = w.mask[l], b.C = (unsigned char*)w.Y[l], b.Cexp = w.Yexp[l];
-            if (l == sk) {  // K = 320: the embedding's four K steps, then the trunk's sixteen
-                b.A2 = (const unsigned char*)w.emb, b.A2exp = w.Eexp, b.bias = w.bias_s[sk];
-                P5_LAUNCH((mlp_gemm5_kernel<4, 0>), Cfg5Skip::LDS, gx, st, b)
-                b.A2 = nullptr, b.A2exp = nullptr;
-            } else if (l == 7 && heads_fused) {  // the last trunk layer with the heads riding along (one wave per SIMD: the form with the registers for it)
-                b.bias = w.bias_s[l];
-                b.hBp = w.Wh4f, b.h_inv = w.wsc_hf, b.h_bias = p->bh, b.h_out = out, b.h_nout = p->n_out;
-                P5_LAUNCH((mlp_gemm5_kernel<0, 2>), Cfg5FwdH::LDS, gx, st, b)
-            } else if (all5) {
-                b.bias = w.bias_s[l];
-                dgm::prof_begin(DGM_STAGE_MLP_LAYER_FWD, st);
-                P5_LAUNCH((mlp_gemm5_kernel<0, 0>), Cfg5Fwd::LDS, gx, st, b)
-                dgm::prof_end(DGM_STAGE_MLP_LAYER_FWD, st);
+    a.ntiles = nt, a.M = N, a.exps_limit = g_env.exps_limit;
+    return a;
+}
+Dw4Args dw4_args(int nt, int tiles_per_chunk, const void* X, const int* Xexp, const void* G, const int* Gexp, float* partial,
+                 size_t chunk_stride, float* partial_db) {
+    Dw4Args d;
+    memset(&d, 0, sizeof(d));
+    d.ntiles = nt, d.tiles_per_chunk = tiles_per_chunk, d.X = (const unsigned char*)X, d.Xexp = Xexp, d.G = (const unsigned char*)G, d.Gexp = Gexp;
+    d.partial = partial, d.chunk_stride = chunk_stride, d.partial_db = partial_db;
+    return d;
+}
+
+// ---- forward ---------------------------------------------------------------------------------------------------------------------
+// The weight-plane jobs both forms have: the forward operand of layer l (or a K slice of it), its backward-data operand, the heads'.
+Prep3Job layer_fwd_job(const dgm_mlp_params* p, int l, int Kp, int hoff, uint4* Bp, float* inv_scale) {
+    return Prep3Job{0, Kp, MLP_W, layer_in(p, l), p->emb_dim, hoff, MLP_W, MLP_W, p->W[l], Bp, inv_scale};
+}
+Prep3Job layer_bwd_job(const dgm_mlp_params* p, int l, const Ws& w) {
+    return Prep3Job{1, MLP_W, MLP_W, layer_in(p, l), p->emb_dim, l == p->skip_layer ? p->emb_dim : 0, MLP_W, MLP_W, p->W[l], w.Wd3[l], w.wsc_d[l]};
+}
+Prep3Job heads_fwd_job(const dgm_mlp_params* p, const Ws& w) {  // B[k][o] = Wh[o][k]
+    return Prep3Job{0, MLP_W, 32, MLP_W, p->emb_dim, 0, MLP_W, p->n_out, p->Wh, w.Wh4f, w.wsc_hf};
+}
+Prep3Job heads_bwd_job(const dgm_mlp_params* p, const Ws& w) {  // B[o][c] = Wh[o][c]
+    return Prep3Job{1, 16, MLP_W, MLP_W, p->emb_dim, 0, p->n_out, MLP_W, p->Wh, w.Wh4b, w.wsc_hb};
+}
+// heads in a launch of their own: out = Y7 Wh^T + bh (one computing wave per workgroup; HBM-bound: one pass over Y7)
+template <bool COLSC>
+int launch_heads(const dgm_mlp_params* p, int N, int nt, int gx, const Ws& w, float* out, hipStream_t st) {
+    Gemm4Args a = gemm4_args(N, nt);
+    a.A = (const unsigned char*)w.Y[7], a.Aexp = w.Yexp[7], a.Bp = w.Wh4f, a.b_inv = w.wsc_hf, a.bias = p->bh;
+    a.out = out, a.ldo = p->n_out, a.n_valid = p->n_out;
+    return launch_lds<mlp_gemm4_kernel<16, 1024, 512, 3, false, 1, COLSC>>(gx, 512, Gemm4Cfg<16, 1024, 512, 3, false, 1, COLSC>::LDS, st, a);
+}
+
+// One time value per call (temb_stride == 0) on round 6's kernel forms: the embedding is 64 columns wide, the time row sits in the
+// biases of layer 0 and the skip layer, the skip layer is one K = 320 GEMM (no `Cin`), the 256-wide layers run one wave per SIMD
+// where that buys something (all5: everywhere, mode 5).
+int forward_folded(const dgm_mlp_params* p, int N, const float* x, const float* temb, const Ws& w, float* out, hipStream_t st,
+                   const bool all5, const float* xadd, const int xadd_stride) {
+    const int nt = p4_plan(N).ntiles, gx = nt < num_cus() ? nt : num_cus(), sk = p->skip_layer;
+    // every weight matrix as two binary16 planes, one power-of-two scale per OUTPUT COLUMN, biases pre-scaled (prep4c_block) ...
+    Prep4cBatch pc;
+    int nc = 0;
+    pc.temb = temb, pc.temb_row = w.temb_row, pc.T = p->t_dim;
+    for (int l = 0; l < 8; l++) {
+        const int Kp = l == 0 ? 64 : (l == sk ? 320 : MLP_W);
+        pc.job[nc++] = Prep4cJob{layer_fwd_job(p, l, Kp, 0, w.Wt3[l], w.wsc_f[l]), p->b[l], w.bias_s[l], (l == 0 || l == sk) ? 1 : 0};
+        if (l >= 1) pc.job[nc++] = Prep4cJob{layer_bwd_job(p, l, w), nullptr, nullptr, 0};
+    }
+    pc.job[nc++] = Prep4cJob{heads_fwd_job(p, w), nullptr, nullptr, 0};
+    pc.job[nc++] = Prep4cJob{heads_bwd_job(p, w), nullptr, nullptr, 0};
+    // ... in ONE launch with the embedding planes (two launches: 13.1 + 10.2 us)
+    const int n_prep = (MLP_W / P4C_COLS) * nc;
+    hipLaunchKernelGGL(mlp_embed4c_kernel, dim3(n_prep + nt), dim3(256), 0, st, N, x, (unsigned char*)w.emb, w.Eexp, 64, pc, n_prep, xadd, xadd_stride);
+    // layer 0: K = 64, eight waves (HBM-bound: 26 MB in, 102 MB of planes out)
+    Gemm4Args a = gemm4_args(N, nt);
+    a.A = (const unsigned char*)w.emb, a.Aexp = w.Eexp, a.Bp = w.Wt3[0], a.b_inv = w.wsc_f[0], a.bias = w.bias_s[0];
+    a.mask_out = w.mask[0], a.C = (unsigned char*)w.Y[0], a.Cexp = w.Yexp[0];
+    if (launch_lds<mlp_gemm4_kernel<4, 256, 128, 0, false, 8, true>>(gx, 512, CfgL0F::LDS, st, a)) return 1;
+    // the heads inside layer 7's launch (mlp_gemm5_kernel<0, 2>) instead of a launch of their own that reads Y_7 again: 64 us against
+    // 50 + 26, +0.95 % on the bench (308.8 / 309.4 / 309.3 against 306.0 / 306.1 / 306.5 it/s, interleaved on one box)
+    const bool heads_fused = g_env.heads_fused;
+    Gemm5Args b;
+    memset(&b, 0, sizeof(b));
+    b.ntiles = nt, b.M = N, b.exps_limit = a.exps_limit;
+    for (int l = 1; l < 8; l++) {
+        b.A = (const unsigned char*)w.Y[l - 1], b.Aexp = w.Yexp[l - 1], b.Bp = w.Wt3[l], b.b_inv = w.wsc_f[l], b.bias = w.bias_s[l];
+        b.mask_out = w.mask[l], b.C = (unsigned char*)w.Y[l], b.Cexp = w.Yexp[l];
+        if (l == sk) {  // K = 320: the embedding's four K steps, then the trunk's sixteen
+            b.A2 = (const unsigned char*)w.emb, b.A2exp = w.Eexp;
+            if (launch_lds<mlp_gemm5_kernel<4, 0>>(gx, 256, Cfg5Skip::LDS, st, b)) return 1;
+            b.A2 = nullptr, b.A2exp = nullptr;
+        } else if (l == 7 && heads_fused) {  // the last trunk layer with the heads riding along (one wave per SIMD: the form with the registers for it)
+            b.hBp = w.Wh4f, b.h_inv = w.wsc_hf, b.h_bias = p->bh, b.h_out = out, b.h_nout = p->n_out;
+            if (launch_lds<mlp_gemm5_kernel<0, 2>>(gx, 256, Cfg5FwdH::LDS, st, b)) return 1;
+        } else {
+            dgm::prof_begin(DGM_STAGE_MLP_LAYER_FWD, st);
+            if (all5) {
+                if (launch_lds<mlp_gemm5_kernel<0, 0>>(gx, 256, Cfg5Fwd::LDS, st, b)) return 1;
             } else {  // the eight-wave form (measured faster for K = 256)
-                a.A = b.A, a.Aexp = b.Aexp, a.Bp = b.Bp, a.b_inv = b.b_inv, a.bias = w.bias_s[l], a.mask_out = b.mask_out, a.C = b.C, a.Cexp = b.Cexp;
-                dgm::prof_begin(DGM_STAGE_MLP_LAYER_FWD, st);
-                P4_LAUNCH((mlp_gemm4_kernel<16, 1024, 512, 0, false, 8, true>), CfgFwdC::LDS, gx, st, a)
-                dgm::prof_end(DGM_STAGE_MLP_LAYER_FWD, st);
+                a.A = b.A, a.Aexp = b.Aexp, a.Bp = b.Bp, a.b_inv = b.b_inv, a.bias = b.bias, a.mask_out = b.mask_out, a.C = b.C, a.Cexp = b.Cexp;
+                if (launch_lds<mlp_gemm4_kernel<16, 1024, 512, 0, false, 8, true>>(gx, 512, CfgFwdC::LDS, st, a)) return 1;
             }
+            dgm::prof_end(DGM_STAGE_MLP_LAYER_FWD, st);
         }
-    } else {
+    }
+    if (!heads_fused && launch_heads<true>(p, N, nt, gx, w, out, st)) return 1;
+    return launch_status();
+}
+
+// Rounds 3-5's kernel forms: a time input per row, and all of mode 4 ("f16x3p8").  The embedding is 96 columns wide, one power-of-two
+// scale per weight matrix, the skip layer's embedding half is an fp32 `Cin` stream that layer 0's launch writes.
+int forward_per_row(const dgm_mlp_params* p, int N, const float* x, const float* temb, int temb_stride, const Ws& w, float* out,
+                    hipStream_t st, const float* xadd, const int xadd_stride) {
+    const int nt = p4_plan(N).ntiles, gx = nt < num_cus() ? nt : num_cus(), sk = p->skip_layer;
+    // embedding planes + the maxima of the nine weight tensors (W_0 .. W_7, Wh)
+    AbsMaxBatch am;
+    am.n_jobs = 9;
+    for (int l = 0; l < 8; l++) am.job[l].W = p->W[l], am.job[l].n = MLP_W * layer_in(p, l);
+    am.job[8].W = p->Wh, am.job[8].n = p->n_out * MLP_W;
+    hipLaunchKernelGGL(mlp_embed4_kernel, dim3(nt + 8 * am.n_jobs), dim3(256), 0, st, N, nt, x, temb, temb_stride, p->t_dim,
+                       (unsigned char*)w.emb, w.Eexp, am, w.matmax, MLP_EMB, xadd, xadd_stride);
+    // every weight matrix as two binary16 planes, one power-of-two scale per matrix (`mat`: its maximum's slot)
+    Prep4Batch pb;
+    int nj = 0;
+    for (int l = 0; l < 8; l++) {
+        if (l == sk) {  // K = 352 = embedding half (rides along with layer 0) | trunk half
+            pb.job[nj++] = Prep4Job{layer_fwd_job(p, l, MLP_EMB, 0, w.Wt3[l], w.wsc_e), l};
+            pb.job[nj++] = Prep4Job{layer_fwd_job(p, l, MLP_W, p->emb_dim, w.Wt3[l] + (size_t)MLP_EMB * MLP_W / 4, w.wsc_f[l]), l};
+        } else
+            pb.job[nj++] = Prep4Job{layer_fwd_job(p, l, layer_kp(p, l), 0, w.Wt3[l], w.wsc_f[l]), l};
+        if (l >= 1) pb.job[nj++] = Prep4Job{layer_bwd_job(p, l, w), l};
+    }
+    pb.job[nj++] = Prep4Job{heads_fwd_job(p, w), 8};
+    pb.job[nj++] = Prep4Job{heads_bwd_job(p, w), 8};
+    hipLaunchKernelGGL(mlp_prep4_kernel, dim3(8, nj), dim3(256), 0, st, pb, w.matmax);
     // layer 0 (K = 96) with the embedding half of the skip layer as second output
+    Gemm4Args a = gemm4_args(N, nt);
     a.A = (const unsigned char*)w.emb, a.Aexp = w.Eexp, a.Bp = w.Wt3[0], a.b_inv = w.wsc_f[0], a.bias = p->b[0];
     a.mask_out = w.mask[0], a.C = (unsigned char*)w.Y[0], a.Cexp = w.Yexp[0];
     a.Bp2 = w.Wt3[sk], a.b_inv2 = w.wsc_e, a.bias2 = p->b[sk], a.out2 = w.Cin;
-    P4_LAUNCH((mlp_gemm4_kernel<6, 384, 192, 0, true, 8>), CfgL0::LDS, gx, st, a)
+    if (launch_lds<mlp_gemm4_kernel<6, 384, 192, 0, true, 8>>(gx, 512, CfgL0::LDS, st, a)) return 1;
     a.Bp2 = nullptr, a.b_inv2 = nullptr, a.bias2 = nullptr, a.out2 = nullptr;
     for (int l = 1; l < 8; l++) {
         a.A = (const unsigned char*)w.Y[l - 1], a.Aexp = w.Yexp[l - 1], a.b_inv = w.wsc_f[l], a.bias = p->b[l];
         a.mask_out = w.mask[l], a.C = (unsigned char*)w.Y[l], a.Cexp = w.Yexp[l];
         if (l == sk) {
             a.Bp = w.Wt3[l] + (size_t)MLP_EMB * MLP_W / 4, a.cin = w.Cin;
-            P4_LAUNCH((mlp_gemm4_kernel<16, 1024, 512, 2, false, 8>), CfgSkip::LDS, gx, st, a)
+            if (launch_lds<mlp_gemm4_kernel<16, 1024, 512, 2, false, 8>>(gx, 512, CfgSkip::LDS, st, a)) return 1;
             a.cin = nullptr;
         } else {
             a.Bp = w.Wt3[l];
             dgm::prof_begin(DGM_STAGE_MLP_LAYER_FWD, st);
-            P4_LAUNCH((mlp_gemm4_kernel<16, 1024, 512, 0, false, 8>), CfgFwd::LDS, gx, st, a)
+            if (launch_lds<mlp_gemm4_kernel<16, 1024, 512, 0, false, 8>>(gx, 512, CfgFwd::LDS, st, a)) return 1;
             dgm::prof_end(DGM_STAGE_MLP_LAYER_FWD, st);
         }
     }
-    }
-    a.Bp2 = nullptr, a.b_inv2 = nullptr, a.bias2 = nullptr, a.out2 = nullptr, a.cin = nullptr;
-    // heads: out = Y7 Wh^T + bh (one computing wave per workgroup; HBM-bound: one pass over Y7)
-    a.A = (const unsigned char*)w.Y[7], a.Aexp = w.Yexp[7], a.Bp = w.Wh4f, a.b_inv = w.wsc_hf, a.bias = p->bh;
-    a.mask_out = nullptr, a.C = nullptr, a.Cexp = nullptr, a.out = out, a.ldo = p->n_out, a.n_valid = p->n_out;
-    if (fold && heads_fused) {}  // (written by layer 7's launch)
-    else if (fold) P4_LAUNCH((mlp_gemm4_kernel<16, 1024, 512, 3, false, 1, true>), CfgHeadsC::LDS, gx, st, a)
-    else P4_LAUNCH((mlp_gemm4_kernel<16, 1024, 512, 3, false, 1>), CfgHeads::LDS, gx, st, a)
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(hipGetErrorString(e));
-    return 0;
+    if (launch_heads<false>(p, N, nt, gx, w, out, st)) return 1;
+    return launch_status();
 }
 
-int backward_planes(const dgm_mlp_params* p, int N, const float* dOut, int temb_stride, const Ws& w, float* const* dW, float* const* db,
-                    float* dWh, float* dbh, float* dtemb, hipStream_t st, const bool fold, const bool all5, const float* x_in = nullptr,
-                    float* dX = nullptr) {
+// ---- backward: the plan ----------------------------------------------------------------------------------------------------------
+// The geometry of a backward pass, computed once per call.  The single-network pass (backward_planes) and the grouped pass
+// (backward_planes_group) both take their row chunks, their partial tiles and their reduction jobs from it through layer_dw():
+// the grouped gradients have the bits of two single passes because there is one statement of all that, not two.
+struct BwdPlan {
+    bool fold;                     // round 6's forms (forward_folded); else rounds 3-5's (forward_per_row)
+    int EW;                        // rows of the embedding's block of the K = EW / EW + 256 weight gradients: 64, or 96 with the time columns
+    int nt, gx;                    // 32-row tiles; workgroups of a launch over all CUs
+    int tiles_per_chunk, chunks;   // stand-alone weight-gradient launches: a chunk is a run of whole tiles, one chunk per CU (or fewer)
+    int n_dw;                      // paired launches (layers 7 .. 1): workgroups on the weight gradient = its row chunks; 0 = two launches
+    int tpc_pair, chunks_pair;     // ... tiles per chunk, ceil(nt / n_dw), and the chunks that have a tile: the last few workgroups may get
+                                   // none and write no partial tile -- the reduction must only read the ones that exist
+    int pair_grid, chunked;        // ... workgroups in all; chunked: the GEMM role walks the weight-gradient role's row chunks
+};
+BwdPlan bwd_plan(int N, bool fold) {
     const P4Plan pl = p4_plan(N);
-    const int nt = pl.ntiles, gx = nt < num_cus() ? nt : num_cus();
-    const int sk = p->skip_layer;
-    const int EW = fold ? 64 : MLP_EMB;  // rows of the embedding's block of the K = EW / EW + 256 weight gradients (fold: see forward_planes)
-    // dOut -> planes (zero columns / rows beyond n_out / N) + the heads' bias-gradient partial sums
-    hipLaunchKernelGGL(mlp_dout4_kernel, dim3((nt + 3) / 4), dim3(256), 0, st, N, nt, p->n_out, dOut, w.Dp, w.Dexp, w.partial_hb);
-    unsigned char* G = (unsigned char*)w.Ga;
-    unsigned char* Gn = (unsigned char*)w.Gb;
-    int *Ge = w.Gexp[0], *Gne = w.Gexp[1];
-    Gemm4Args a;
-    memset(&a, 0, sizeof(a));
-    a.ntiles = nt, a.M = N, a.exps_limit = p4_exps_limit();
-    // G_7 = (dOut Wh) masked by layer 7's ReLU
-    a.A = w.Dp, a.Aexp = w.Dexp, a.Bp = w.Wh4b, a.b_inv = w.wsc_hb, a.mask_in = w.mask[7], a.C = G, a.Cexp = Ge;
-    Dw4Args d;
-    memset(&d, 0, sizeof(d));
-    d.ntiles = nt, d.tiles_per_chunk = pl.tiles_per_chunk;
-    // heads' weight gradient: dWh[o][c] = sum_r dOut[r][o] Y7[r][c]
-    d.X = (const unsigned char*)w.Y[7], d.Xexp = w.Yexp[7], d.G = w.Dp, d.Gexp = w.Dexp, d.partial = w.partial_h, d.chunk_stride = 0;
-    d.partial_db = nullptr;
-    // (tried, round 6: this launch on a side stream beside the G_7 launch -- a read stream over Y_7 beside a write stream, joined again in
-    // front of the reduction; G_7 with one or two workgroups per CU: 308.8 / 309.0 and 306.3 / 308.2 it/s against 311.7 / 311.8 in order)
-    {   // one K step per tile: nothing to hide the epilogue's barriers under, so two workgroups per CU (104 VGPRs, 54 KB of LDS)
-        static const int mult = [] { const char* e = getenv("DGM_P4_G7_MULT"); return e ? atoi(e) : 2; }();
-        const int g7 = nt < mult * num_cus() ? nt : mult * num_cus();
-        if (fold) P4_LAUNCH((mlp_gemm4_kernel<1, 128, 64, 1, false, 8, true>), CfgG7C::LDS, g7, st, a)
-        else P4_LAUNCH((mlp_gemm4_kernel<1, 128, 64, 1, false, 8>), CfgG7::LDS, g7, st, a)
+    BwdPlan b;
+    b.fold = fold, b.EW = fold ? 64 : MLP_EMB;
+    b.nt = pl.ntiles, b.gx = b.nt < num_cus() ? b.nt : num_cus();
+    b.tiles_per_chunk = pl.tiles_per_chunk, b.chunks = pl.chunks;
+    // backward data (G_l -> G_{l-1}) and the weight gradient of layer l both consume G_l and nothing of each other: ONE launch, the
+    // first n_dw workgroups on the weight gradient, the rest on the layer GEMM (mlp_bwd_pair_kernel).  Small problems have nothing to
+    // balance; DGM_MLP_PAIR=<n> overrides the share (0: two launches over all CUs).
+    b.n_dw = 0;
+    if (b.gx >= 64 && b.nt >= 4 * b.gx) {
+        b.n_dw = g_env.pair >= 0 ? g_env.pair : (b.gx * P4_PAIR_SHARE_NUM) / P4_PAIR_SHARE_DEN;
+        if (b.n_dw >= b.gx) b.n_dw = b.gx - 1;
+        if (b.n_dw > b.chunks) b.n_dw = b.chunks;  // (the skip layer's partial buffer is carved for pl.chunks tiles of 352 rows)
     }
-    P4_LAUNCH((mlp_dw4_kernel<8, 1, 1024, 512, 128, 64>), CfgDwH::LDS, pl.chunks, st, d)
-    ReduceDwBatch rb;
-    rb.n_jobs = 0;
-    int rb_blocks = 0, n_pending = 0;
-    auto add_job = [&](int slot, int chunks, int db_rows, int Kp, int in_features, int dst_off, const float* partial,
-                       const float* partial_db, float* dWp, float* dbp) {
-        ReduceDwJob& jb = rb.job[slot];
-        jb.chunks = chunks, jb.db_rows = db_rows, jb.Kp = Kp, jb.in_features = in_features, jb.nblocks = reduce_dw_blocks(Kp);
-        jb.first_block = 0, jb.emb_rows = EW, jb.k_valid = fold ? MLP_XE : p->emb_dim, jb.emb_dim = p->emb_dim;
-        jb.dst_off = dst_off, jb.partial = partial, jb.partial_db = partial_db, jb.dW = dWp, jb.db = dbp;
-        if (jb.nblocks > rb_blocks) rb_blocks = jb.nblocks;
+    b.tpc_pair = b.n_dw > 0 ? (b.nt + b.n_dw - 1) / b.n_dw : 0;
+    b.chunks_pair = b.n_dw > 0 ? (b.nt + b.tpc_pair - 1) / b.tpc_pair : 0;
+    b.pair_grid = b.n_dw + (b.gx - b.n_dw > 0 ? b.gx - b.n_dw : 1);
+    // chunked needs as many GEMM workgroups as chunks, and ids w, n_dw + w on the same XCD: G_l's second read then hits that XCD's
+    // L2, -97 MB of fabric traffic per launch at the same kernel time (profiles/r04_pmc_bwd_pair.json)
+    b.chunked = (b.pair_grid - b.n_dw == b.n_dw && (b.n_dw % 8) == 0) ? 1 : 0;
+    return b;
+}
+// workgroups per role and network of a grouped paired launch: half of the chunks, a multiple of 8; 0 = no grouping
+int group_split(const BwdPlan& bp) {
+    const int n_wg = (bp.n_dw / 2) & ~7;
+    return (n_wg < 8 || 4 * n_wg > bp.gx) ? 0 : n_wg;
+}
+// The weight gradient of layer l of one network: the arguments of its launches, and its reduction job(s) queued into
+// rb.job[slot], rb.job[slot + step] (the caller counts them into rb.n_jobs: a grouped pass interleaves its two networks, step = 2).
+struct LayerDw {
+    Dw4Args emb;       // layers 0 and skip: the embedding's rows (rows 0 .. EW - 1 of the K = EW / EW + 256 gradient) with the layer's bias
+                       // gradient: always a stand-alone launch of bp.chunks chunks (own partial tiles; paired skip layer: own reduction job)
+    Dw4Args trunk;     // layers >= 1: the trunk's rows -- the weight-gradient role of the paired launch, or a stand-alone launch
+    int trunk_chunks;  // ... its chunks
+    int n_jobs;
+};
+LayerDw layer_dw(const BwdPlan& bp, const dgm_mlp_params* p, const Ws& w, int l, const unsigned char* G, const int* Ge, float* const* dW,
+                 float* const* db, ReduceDwBatch& rb, int slot, int step) {
+    const int sk = p->skip_layer, EW = bp.EW;
+    const bool paired = bp.n_dw > 0 && l >= 1, split = paired && l == sk;
+    const int Kp = l == 0 ? EW : (l == sk ? EW + MLP_W : MLP_W);
+    LayerDw g;
+    memset(&g, 0, sizeof(g));
+    g.trunk_chunks = paired ? bp.chunks_pair : bp.chunks;
+    g.n_jobs = split ? 2 : 1;
+    // partial tiles of the layer: [chunk][Kp][256]; paired skip layer: trunk rows [n_dw][256][256], then embedding rows [chunks][EW][256]
+    float* part_emb = w.partial_l[l];
+    float* part_trunk = w.partial_l[l] + (l == sk ? (size_t)EW * MLP_W : 0);
+    size_t stride_emb = (size_t)Kp * MLP_W, stride_trunk = (size_t)Kp * MLP_W;
+    if (split) {
+        part_trunk = w.partial_l[l], stride_trunk = (size_t)MLP_W * MLP_W;
+        part_emb = w.partial_l[l] + (size_t)bp.n_dw * MLP_W * MLP_W, stride_emb = (size_t)EW * MLP_W;
+    }
+    if (l == 0 || l == sk) g.emb = dw4_args(bp.nt, bp.tiles_per_chunk, w.emb, w.Eexp, G, Ge, part_emb, stride_emb, w.partial_db_l[l]);
+    if (l >= 1)  // (the skip layer's bias gradient came with its embedding half)
+        g.trunk = dw4_args(bp.nt, paired ? bp.tpc_pair : bp.tiles_per_chunk, w.Y[l - 1], w.Yexp[l - 1], G, Ge, part_trunk, stride_trunk,
+                           l == sk ? nullptr : w.partial_db_l[l]);
+    auto job = [&](int at, int chunks, int db_rows, int jKp, int dst_off, const float* partial, const float* partial_db, float* dbp) {
+        ReduceDwJob& jb = rb.job[at];
+        jb.chunks = chunks, jb.db_rows = db_rows, jb.Kp = jKp, jb.in_features = layer_in(p, l), jb.nblocks = reduce_dw_blocks(jKp);
+        jb.first_block = 0, jb.emb_rows = EW, jb.k_valid = bp.fold ? MLP_XE : p->emb_dim, jb.emb_dim = p->emb_dim;
+        jb.dst_off = dst_off, jb.partial = partial, jb.partial_db = partial_db, jb.dW = dW[l], jb.db = dbp;
     };
-    // Layers 7 .. 1: backward data (G_l -> G_{l-1}) and the weight gradient of layer l both consume G_l and nothing of each
-    // other: ONE launch, the first n_dw workgroups on the weight gradient (n_dw row chunks), the rest on the layer GEMM
-    // (mlp_bwd_pair_kernel).  n_dw = 0 (DGM_MLP_PAIR=0) runs them as two launches over all CUs.  The embedding's rows of the
-    // skip layer's gradient stay a launch of their own over all CUs (own partial tiles, own reduction job).
-    int n_dw = p4_pair_split(nt, gx);
-    if (n_dw > pl.chunks) n_dw = pl.chunks;  // (the skip layer's partial buffer is carved for pl.chunks tiles of 352 rows)
+    if (split) {  // two reduction jobs: embedding rows (with the bias gradient), trunk rows
+        job(slot, bp.chunks, 8 * bp.chunks, EW, 0, part_emb, w.partial_db_l[l], db[l]);
+        job(slot + step, g.trunk_chunks, 0, MLP_W, p->emb_dim, part_trunk, nullptr, nullptr);
+    } else
+        job(slot, g.trunk_chunks, 8 * g.trunk_chunks, Kp, 0, w.partial_l[l], w.partial_db_l[l], db[l]);
+    return g;
+}
+// The pass's ONE reduction launch: all queued jobs (blockIdx.y = job; every layer keeps its partial tiles until then) and the heads'
+// partial sums of n_nets networks.
+void set_heads(ReduceDwBatch::Heads& h, const BwdPlan& bp, const dgm_mlp_params* p, const Ws& w, float* dWh, float* dbh) {
+    h.chunks = bp.chunks, h.bchunks = bp.nt, h.nout = p->n_out;
+    h.partial_W = w.partial_h, h.partial_b = w.partial_hb, h.dW = dWh, h.db = dbh;
+}
+void launch_reduce_all(const ReduceDwBatch& rb, int n_nets, hipStream_t st) {
+    int gx = 0;
+    for (int i = 0; i < rb.n_jobs; i++) gx = rb.job[i].nblocks > gx ? rb.job[i].nblocks : gx;
+    hipLaunchKernelGGL(mlp_reduce_dw_all_kernel, dim3(gx, rb.n_jobs + n_nets), dim3(256), 0, st, rb);
+}
+
+// ---- backward: one network ---------------------------------------------------------------------------------------------------------
+// COLSC: the pass's form, chosen once per call -- round 6's (one weight scale per output column, the time row folded: forward_folded)
+// or rounds 3-5's.  all5 (mode 5, COLSC only): the unpaired backward-data GEMMs in the one-wave-per-SIMD form.
+template <bool COLSC>
+int backward_planes(const dgm_mlp_params* p, int N, const float* dOut, int temb_stride, const Ws& w, float* const* dW, float* const* db,
+                    float* dWh, float* dbh, float* dtemb, hipStream_t st, const bool all5, const float* x_in, float* dX) {
+    const BwdPlan bp = bwd_plan(N, COLSC);
+    const int nt = bp.nt, gx = bp.gx, sk = p->skip_layer;
     const bool per_row_t = temb_stride != 0 && dtemb != nullptr;
     if (per_row_t && dX) return fail("mlp_backward: position gradients need a broadcast time row");
+    // dOut -> planes (zero columns / rows beyond n_out / N) + the heads' bias-gradient partial sums
+    hipLaunchKernelGGL(mlp_dout4_kernel, dim3((nt + 3) / 4), dim3(256), 0, st, N, nt, p->n_out, dOut, w.Dp, w.Dexp, w.partial_hb);
+    unsigned char *G = (unsigned char*)w.Ga, *Gn = (unsigned char*)w.Gb;
+    int *Ge = w.Gexp[0], *Gne = w.Gexp[1];
+    // G_7 = (dOut Wh) masked by layer 7's ReLU.  One K step per tile: nothing to hide the epilogue's barriers under, so two workgroups
+    // per CU (104 VGPRs, 54 KB of LDS; one per CU: 306.3 / 308.2 it/s against 308.8 / 309.0)
+    // (tried, round 6: the heads' weight gradient on a side stream beside this launch -- a read stream over Y_7 beside a write stream,
+    // joined again in front of the reduction: 308.8 / 309.0 it/s against 311.7 / 311.8 in order)
+    Gemm4Args a = gemm4_args(N, nt);
+    a.A = w.Dp, a.Aexp = w.Dexp, a.Bp = w.Wh4b, a.b_inv = w.wsc_hb, a.mask_in = w.mask[7], a.C = G, a.Cexp = Ge;
+    const int g7 = nt < 2 * num_cus() ? nt : 2 * num_cus();
+    if (launch_lds<mlp_gemm4_kernel<1, 128, 64, 1, false, 8, COLSC>>(g7, 512, Gemm4Cfg<1, 128, 64, 1, false, 8, COLSC>::LDS, st, a)) return 1;
+    // heads' weight gradient: dWh[o][c] = sum_r dOut[r][o] Y7[r][c]
+    const Dw4Args dh = dw4_args(nt, bp.tiles_per_chunk, w.Y[7], w.Yexp[7], w.Dp, w.Dexp, w.partial_h, 0, nullptr);
+    if (launch_lds<mlp_dw4_kernel<8, 1, 1024, 512, 128, 64>>(bp.chunks, 512, CfgDwH::LDS, st, dh)) return 1;
+    ReduceDwBatch rb;
+    memset(&rb, 0, sizeof(rb));
+    // Layers 7 .. 1: the paired launch, or (n_dw = 0) backward data and weight gradient as two launches over all CUs.  The embedding's
+    // rows of the skip layer's gradient stay a launch of their own over all CUs.
     for (int l = 7; l >= 0; l--) {
-        const int Kp = l == 0 ? EW : (l == sk ? EW + MLP_W : MLP_W);
-        const bool paired = n_dw > 0 && l >= 1;
-        // (the paired launch gives each of its n_dw weight-gradient workgroups ceil(nt / n_dw) tiles: the last few may get none
-        // and write no partial tile -- the reduction must only read the ones that exist)
-        const int tpc_pair = paired ? (nt + n_dw - 1) / n_dw : 0;
-        const int chunks_l = paired ? (nt + tpc_pair - 1) / tpc_pair : pl.chunks;
-        if (l >= 1) {  // backward data: G_{l-1} = (G_l W_l) masked, into the other buffer
+        if (l >= 1)  // backward data: G_{l-1} = (G_l W_l) masked, into the other buffer
             a.A = G, a.Aexp = Ge, a.Bp = w.Wd3[l], a.b_inv = w.wsc_d[l], a.mask_in = w.mask[l - 1], a.C = Gn, a.Cexp = Gne;
-        }
-        d.G = G, d.Gexp = Ge;
         if (dX && (l == sk || l == 0))  // gradient w.r.t. the positions: G_5 W_5[:, :63] into scratch (the forward's Cin, idle now), then + G_0 W_0[:, :63] and PE'
             hipLaunchKernelGGL(mlp_dx4_kernel, dim3(nt), dim3(256), 0, st, N, (const unsigned char*)G, (const int*)Ge, p->W[l],
                                layer_in(p, l), 0, MLP_XE, reinterpret_cast<float*>(w.Cin), l == 0 ? 1 : 0, x_in, dX, 0);
@@ -1096,70 +1166,36 @@ int backward_planes(const dgm_mlp_params* p, int N, const float* dOut, int temb_
             hipLaunchKernelGGL(mlp_dx4_kernel, dim3(nt), dim3(256), 0, st, N, (const unsigned char*)G, (const int*)Ge, p->W[l],
                                layer_in(p, l), MLP_XE, p->t_dim, reinterpret_cast<float*>(w.Cin), l == 0 ? 2 : 0, (const float*)nullptr,
                                dtemb, p->t_dim);
-        // partial tiles of the layer: [chunk][Kp][256]; paired skip layer: trunk rows [n_dw][256][256], then embedding rows [chunks][96][256]
-        float* part_emb = w.partial_l[l];
-        float* part_trunk = w.partial_l[l] + (l == sk ? (size_t)EW * MLP_W : 0);
-        size_t stride_emb = (size_t)Kp * MLP_W, stride_trunk = (size_t)Kp * MLP_W;
-        if (paired && l == sk) {
-            part_trunk = w.partial_l[l], stride_trunk = (size_t)MLP_W * MLP_W;
-            part_emb = w.partial_l[l] + (size_t)n_dw * MLP_W * MLP_W, stride_emb = (size_t)EW * MLP_W;
-        }
-        if (l == 0 || l == sk) {  // the embedding's rows of the gradient (rows 0 .. 95 of the K = 96 / 352 partial tile)
-            d.tiles_per_chunk = pl.tiles_per_chunk;
-            d.X = (const unsigned char*)w.emb, d.Xexp = w.Eexp, d.partial = part_emb, d.chunk_stride = stride_emb, d.partial_db = w.partial_db_l[l];
-            if (fold) P4_LAUNCH((mlp_dw4_kernel<2, 8, 256, 128, 1024, 512>), CfgDwE64::LDS, pl.chunks, st, d)
-            else P4_LAUNCH((mlp_dw4_kernel<3, 8, 384, 192, 1024, 512>), CfgDwE::LDS, pl.chunks, st, d)
-        }
-        if (l != 0) {
-            d.tiles_per_chunk = paired ? tpc_pair : pl.tiles_per_chunk;
-            d.X = (const unsigned char*)w.Y[l - 1], d.Xexp = w.Yexp[l - 1];
-            d.partial = part_trunk, d.chunk_stride = stride_trunk;
-            d.partial_db = l == sk ? nullptr : w.partial_db_l[l];  // (the skip layer's bias gradient came with its embedding half)
-        }
-        if (paired) {
-            dgm::prof_begin(DGM_STAGE_MLP_BWD_PAIR, st);
-            {
-                static bool done_[DGM_MAX_DEVICES] = {false}, donec_[DGM_MAX_DEVICES] = {false};
-                constexpr int LDS_PAIR = CfgBwdC::LDS > CfgDw::LDS ? CfgBwdC::LDS : CfgDw::LDS;
-                if ((fold ? p4_lds_attr(mlp_bwd_pair_kernel<true>, LDS_PAIR, &donec_[current_device_slot()])
-                          : p4_lds_attr(mlp_bwd_pair_kernel<false>, LDS_PAIR, &done_[current_device_slot()])) != hipSuccess)
-                    return fail("mlp: cannot raise the LDS limit of mlp_bwd_pair_kernel");
-                const int grid = n_dw + (gx - n_dw > 0 ? gx - n_dw : 1);
-                // chunked: the GEMM role walks the weight-gradient role's row chunks (needs as many GEMM workgroups as chunks)
-                static const int chunk_env = [] { const char* e = getenv("DGM_MLP_PAIR_CHUNKED"); return e ? atoi(e) : 1; }();
-                const int chunked = (chunk_env && grid - n_dw == n_dw && (n_dw % 8) == 0) ? 1 : 0;
-                if (fold) hipLaunchKernelGGL(mlp_bwd_pair_kernel<true>, dim3(grid), dim3(512), LDS_PAIR, st, a, d, n_dw, chunked);
-                else hipLaunchKernelGGL(mlp_bwd_pair_kernel<false>, dim3(grid), dim3(512), LDS_PAIR, st, a, d, n_dw, chunked);
+        const LayerDw g = layer_dw(bp, p, w, l, G, Ge, dW, db, rb, rb.n_jobs, 1);
+        rb.n_jobs += g.n_jobs;
+        if (l == 0 || l == sk) {
+            if constexpr (COLSC) {
+                if (launch_lds<mlp_dw4_kernel<2, 8, 256, 128, 1024, 512>>(bp.chunks, 512, CfgDwE64::LDS, st, g.emb)) return 1;
+            } else {
+                if (launch_lds<mlp_dw4_kernel<3, 8, 384, 192, 1024, 512>>(bp.chunks, 512, CfgDwE::LDS, st, g.emb)) return 1;
             }
+        }
+        if (l == 0) break;
+        if (bp.n_dw > 0) {
+            dgm::prof_begin(DGM_STAGE_MLP_BWD_PAIR, st);
+            if (launch_lds<mlp_bwd_pair_kernel<COLSC>>(bp.pair_grid, 512, LDS_PAIR, st, a, g.trunk, bp.n_dw, bp.chunked)) return 1;
             dgm::prof_end(DGM_STAGE_MLP_BWD_PAIR, st);
-        } else if (l >= 1) {
+        } else {
             dgm::prof_begin(DGM_STAGE_MLP_LAYER_BWD, st);
             if (all5) {
                 Gemm5Args b;
                 memset(&b, 0, sizeof(b));
                 b.ntiles = nt, b.M = N, b.exps_limit = a.exps_limit;
                 b.A = a.A, b.Aexp = a.Aexp, b.Bp = a.Bp, b.b_inv = a.b_inv, b.mask_in = a.mask_in, b.C = a.C, b.Cexp = a.Cexp;
-                P5_LAUNCH((mlp_gemm5_kernel<0, 1>), Cfg5Bwd::LDS, gx, st, b)
-            } else if (fold)
-                P4_LAUNCH((mlp_gemm4_kernel<16, 1024, 512, 1, false, 8, true>), CfgBwdC::LDS, gx, st, a)
-            else
-                P4_LAUNCH((mlp_gemm4_kernel<16, 1024, 512, 1, false, 8>), CfgBwd::LDS, gx, st, a)
+                if (launch_lds<mlp_gemm5_kernel<0, 1>>(gx, 256, Cfg5Bwd::LDS, st, b)) return 1;
+            } else if (launch_lds<mlp_gemm4_kernel<16, 1024, 512, 1, false, 8, COLSC>>(gx, 512, Gemm4Cfg<16, 1024, 512, 1, false, 8, COLSC>::LDS, st, a))
+                return 1;
             dgm::prof_end(DGM_STAGE_MLP_LAYER_BWD, st);
             dgm::prof_begin(DGM_STAGE_MLP_LAYER_DW, st);
-            P4_LAUNCH((mlp_dw4_kernel<8, 8, 1024, 512, 1024, 512>), CfgDw::LDS, chunks_l, st, d)
+            if (launch_lds<mlp_dw4_kernel<8, 8, 1024, 512, 1024, 512>>(g.trunk_chunks, 512, CfgDw::LDS, st, g.trunk)) return 1;
             dgm::prof_end(DGM_STAGE_MLP_LAYER_DW, st);
         }
-        if (paired && l == sk) {  // two reduction jobs: embedding rows (with the bias gradient), trunk rows
-            add_job(n_pending++, pl.chunks, 8 * pl.chunks, EW, layer_in(p, l), 0, part_emb, w.partial_db_l[l], dW[l], db[l]);
-            add_job(n_pending++, chunks_l, 0, MLP_W, layer_in(p, l), p->emb_dim, part_trunk, nullptr, dW[l], nullptr);
-        } else
-            add_job(n_pending++, chunks_l, 8 * chunks_l, Kp, layer_in(p, l), 0, w.partial_l[l], w.partial_db_l[l], dW[l], db[l]);
-        if (l >= 1) {
-            unsigned char* t = G;
-            G = Gn, Gn = t;
-            int* te = Ge;
-            Ge = Gne, Gne = te;
-        }
+        std::swap(G, Gn), std::swap(Ge, Gne);
     }
     // (tried: the previous layer's partial tiles summed by the GEMM workgroups of the next paired launch, before their weight
     // prologue: the launch grows by 9 us (87 -> 96), six launches, while this reduction only shrinks 87 -> 52 us: a net loss)
@@ -1175,11 +1211,9 @@ int backward_planes(const dgm_mlp_params* p, int N, const float* dOut, int temb_
     // forward pass, showed +2 % -- that overlap is not available to a correct step)
     // (tried: each layer's reduction on a side stream under the next layer's launch -- its small workgroups do fit beside a
     // resident pair workgroup -- 265 vs 274 it/s: slower, the pair kernel's HBM-bound half gets the competition)
-    rb.n_jobs = n_pending;
-    rb.heads[0].chunks = pl.chunks, rb.heads[0].bchunks = nt, rb.heads[0].nout = p->n_out;
-    rb.heads[0].partial_W = w.partial_h, rb.heads[0].partial_b = w.partial_hb, rb.heads[0].dW = dWh, rb.heads[0].db = dbh;
-    hipLaunchKernelGGL(mlp_reduce_dw_all_kernel, dim3(rb_blocks, rb.n_jobs + 1), dim3(256), 0, st, rb);
-    if (fold) {  // the time columns of dW_0 / dW_skip: db (x) t_emb; and dL/dt_emb (one launch)
+    set_heads(rb.heads[0], bp, p, w, dWh, dbh);
+    launch_reduce_all(rb, 1, st);
+    if constexpr (COLSC) {  // the time columns of dW_0 / dW_skip: db (x) t_emb; and dL/dt_emb (one launch)
         FoldGradArgs f;
         f.dW[0] = dW[0], f.db[0] = db[0], f.W[0] = p->W[0], f.in_features[0] = layer_in(p, 0);
         f.dW[1] = dW[sk], f.db[1] = db[sk], f.W[1] = p->W[sk], f.in_features[1] = layer_in(p, sk);
@@ -1188,16 +1222,14 @@ int backward_planes(const dgm_mlp_params* p, int N, const float* dOut, int temb_
     } else if (dtemb != nullptr && !per_row_t)
         hipLaunchKernelGGL(mlp_dtemb_bcast_kernel, dim3(p->t_dim), dim3(256), 0, st, p->t_dim, db[0], p->W[0], layer_in(p, 0),
                            db[sk], p->W[sk], layer_in(p, sk), dtemb);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(hipGetErrorString(e));
-    return 0;
+    return launch_status();
 }
 
-// ---- two networks' backward passes in shared launches (dgm_mlp_backward_group) -----------------------------------------------------
+// ---- backward: two networks in shared launches (dgm_mlp_backward_group) -------------------------------------------------------------
 // The folded f16x3p forms with the paired launches only (the caller falls back to two ordinary passes otherwise).  Layers 7 .. 0
-// are walked once; every launch of backward_planes() appears once and serves both networks (the group kernels of
-// mlp_planes.hpp).  The row chunks of every weight gradient, their partial tiles and the reduction's jobs are those of
-// backward_planes(): the gradients are bit-identical to two ordinary passes.  What the grouping saves is launches (eleven per
+// are walked once; every launch of backward_planes<true>() appears once and serves both networks (the group kernels of
+// mlp_planes.hpp).  The row chunks of every weight gradient, their partial tiles and the reduction's jobs come from the same
+// bwd_plan() / layer_dw(): the gradients are bit-identical to two ordinary passes.  What the grouping saves is launches (eleven per
 // step), the layer GEMM's weight prologue per tile, and the tail of a launch whose tiles do not divide by its workgroups.
 struct GroupNet {
     const dgm_mlp_params* p;
@@ -1207,29 +1239,9 @@ struct GroupNet {
     float* const* db;
     float *dWh, *dbh, *dtemb;
 };
-// weight-gradient chunks per network of a paired launch, as backward_planes() has them; 0 = pairing off
-int p4_pair_chunks(int N) {
-    const P4Plan pl = p4_plan(N);
-    const int nt = pl.ntiles, gx = nt < num_cus() ? nt : num_cus();
-    int n_dw = p4_pair_split(nt, gx);
-    if (n_dw > pl.chunks) n_dw = pl.chunks;
-    return n_dw;
-}
-// workgroups per role and network of a grouped paired launch: half of the chunks, a multiple of 8; 0 = no grouping
-int p4_group_split(int N) {
-    const P4Plan pl = p4_plan(N);
-    const int nt = pl.ntiles, gx = nt < num_cus() ? nt : num_cus();
-    const int n_wg = (p4_pair_chunks(N) / 2) & ~7;
-    if (n_wg < 8 || 4 * n_wg > gx) return 0;
-    return n_wg;
-}
-int backward_planes_group(const GroupNet* nets, int N, const int n_wg, hipStream_t st) {
-    const P4Plan pl = p4_plan(N);
-    const int nt = pl.ntiles, sk = 5, EW = 64;
-    const int n_dw = p4_pair_chunks(N);                      // a network's weight-gradient chunks, as in backward_planes()
-    const int cpw = (n_dw + n_wg - 1) / n_wg;                // ... of which a workgroup runs this many
-    const int tpc_s = pl.tiles_per_chunk, chunks_s = pl.chunks;  // stand-alone weight-gradient launches: backward_planes()'s chunks, blockIdx.y = network
-    const int tpc_pair = (nt + n_dw - 1) / n_dw, chunks_pair = (nt + tpc_pair - 1) / tpc_pair;  // (the last few chunks may have no tile and write none)
+int backward_planes_group(const GroupNet* nets, int N, const BwdPlan& bp, const int n_wg, hipStream_t st) {
+    const int nt = bp.nt, sk = 5;
+    const int cpw = (bp.n_dw + n_wg - 1) / n_wg;  // weight-gradient chunks of a network that one workgroup runs
     {
         Dout4GroupArgs da;
         for (int i = 0; i < 2; i++)
@@ -1241,44 +1253,22 @@ int backward_planes_group(const GroupNet* nets, int N, const int n_wg, hipStream
     int *Ge[2], *Gne[2];
     PairGroupArgs pg;
     memset(&pg, 0, sizeof(pg));
+    Gemm4GroupArgs g7a;  // G_7 = (dOut Wh) masked by layer 7's ReLU: two workgroups per CU in all, as in backward_planes()
+    Dw4GroupArgs dg;     // heads' weight gradient: dWh[o][c] = sum_r dOut[r][o] Y7[r][c]
+    memset(&dg, 0, sizeof(dg));
     for (int i = 0; i < 2; i++) {
         const Ws& w = nets[i].w;
         G[i] = (unsigned char*)w.Ga, Gn[i] = (unsigned char*)w.Gb, Ge[i] = w.Gexp[0], Gne[i] = w.Gexp[1];
-        pg.ga[i].ntiles = nt, pg.ga[i].M = N, pg.ga[i].exps_limit = p4_exps_limit();
-        pg.da[i].ntiles = nt;
+        pg.ga[i] = gemm4_args(N, nt);
+        Gemm4Args& a = g7a.a[i];
+        a = pg.ga[i];
+        a.A = w.Dp, a.Aexp = w.Dexp, a.Bp = w.Wh4b, a.b_inv = w.wsc_hb, a.mask_in = w.mask[7], a.C = G[i], a.Cexp = Ge[i];
+        dg.a[i] = dw4_args(nt, bp.tiles_per_chunk, w.Y[7], w.Yexp[7], w.Dp, w.Dexp, w.partial_h, 0, nullptr);
     }
-    {   // G_7 = (dOut Wh) masked by layer 7's ReLU: two workgroups per CU in all, as in backward_planes()
-        Gemm4GroupArgs g7a;
-        for (int i = 0; i < 2; i++) {
-            const Ws& w = nets[i].w;
-            Gemm4Args& a = g7a.a[i];
-            a = pg.ga[i];
-            a.A = w.Dp, a.Aexp = w.Dexp, a.Bp = w.Wh4b, a.b_inv = w.wsc_hb, a.mask_in = w.mask[7], a.C = G[i], a.Cexp = Ge[i];
-        }
-        const int g7 = nt < num_cus() ? nt : num_cus();
-        static bool done_[DGM_MAX_DEVICES] = {false};
-        if (p4_lds_attr(mlp_gemm4_group_kernel<1, 128, 64, 1, false, 8, true>, CfgG7C::LDS, &done_[current_device_slot()]) != hipSuccess)
-            return fail("mlp: cannot raise the LDS limit of a plane-path kernel");
-        hipLaunchKernelGGL((mlp_gemm4_group_kernel<1, 128, 64, 1, false, 8, true>), dim3(g7, 2), dim3(512), CfgG7C::LDS, st, g7a);
-    }
-    Dw4GroupArgs dg;
-    memset(&dg, 0, sizeof(dg));
-    {   // heads' weight gradient: dWh[o][c] = sum_r dOut[r][o] Y7[r][c]
-        for (int i = 0; i < 2; i++) {
-            const Ws& w = nets[i].w;
-            Dw4Args& d = dg.a[i];
-            d.ntiles = nt, d.tiles_per_chunk = tpc_s;
-            d.X = (const unsigned char*)w.Y[7], d.Xexp = w.Yexp[7], d.G = w.Dp, d.Gexp = w.Dexp, d.partial = w.partial_h, d.chunk_stride = 0;
-            d.partial_db = nullptr;
-        }
-        static bool done_[DGM_MAX_DEVICES] = {false};
-        if (p4_lds_attr(mlp_dw4_group_kernel<8, 1, 1024, 512, 128, 64>, CfgDwH::LDS, &done_[current_device_slot()]) != hipSuccess)
-            return fail("mlp: cannot raise the LDS limit of a plane-path kernel");
-        hipLaunchKernelGGL((mlp_dw4_group_kernel<8, 1, 1024, 512, 128, 64>), dim3(chunks_s, 2), dim3(512), CfgDwH::LDS, st, dg);
-    }
+    if (launch_lds<mlp_gemm4_group_kernel<1, 128, 64, 1, false, 8, true>>(dim3(bp.gx, 2), 512, Gemm4Cfg<1, 128, 64, 1, false, 8, true>::LDS, st, g7a)) return 1;
+    if (launch_lds<mlp_dw4_group_kernel<8, 1, 1024, 512, 128, 64>>(dim3(bp.chunks, 2), 512, CfgDwH::LDS, st, dg)) return 1;
     ReduceDwBatch rb;
     memset(&rb, 0, sizeof(rb));
-    int rb_blocks = 0, n_pending = 0;
     // Reduce role of the paired launches (pair_reduce_role, mlp_planes.hpp): the launch of layer l reduces the first n_hidden pieces
     // of layer l + 1's K = 256 jobs, whose tiles the launch before it wrote.  Layer 7's launch has nothing to reduce yet, layer 1's
     // jobs have no launch behind them: six of the seven layers can be hidden.
@@ -1286,44 +1276,20 @@ int backward_planes_group(const GroupNet* nets, int N, const int n_wg, hipStream
     PairReduceArgs pr;
     memset(&pr, 0, sizeof(pr));
     int hidden_slot[2] = {0, 0};  // rb.job slots of the K = 256 jobs the previous paired launch's tiles belong to
-    auto add_job = [&](const dgm_mlp_params* p, int chunks, int db_rows, int Kp, int in_features, int dst_off, const float* partial,
-                       const float* partial_db, float* dWp, float* dbp) {
-        ReduceDwJob& jb = rb.job[n_pending++];
-        jb.chunks = chunks, jb.db_rows = db_rows, jb.Kp = Kp, jb.in_features = in_features, jb.nblocks = reduce_dw_blocks(Kp);
-        jb.first_block = 0, jb.emb_rows = EW, jb.k_valid = MLP_XE, jb.emb_dim = nets[0].p->emb_dim;  // (the caller checked: the same for both networks)
-        jb.dst_off = dst_off, jb.partial = partial, jb.partial_db = partial_db, jb.dW = dWp, jb.db = dbp;
-        if (jb.nblocks > rb_blocks) rb_blocks = jb.nblocks;
-    };
     for (int l = 7; l >= 0; l--) {
-        if (l == 0 || l == sk) {  // the embedding's rows of the gradient, with the layer's bias gradient
-            for (int i = 0; i < 2; i++) {
-                const Ws& w = nets[i].w;
-                Dw4Args& d = dg.a[i];
-                d.ntiles = nt, d.tiles_per_chunk = tpc_s;
-                d.X = (const unsigned char*)w.emb, d.Xexp = w.Eexp, d.G = G[i], d.Gexp = Ge[i];
-                d.partial = l == sk ? w.partial_l[l] + (size_t)n_dw * MLP_W * MLP_W : w.partial_l[l];
-                d.chunk_stride = (size_t)EW * MLP_W, d.partial_db = w.partial_db_l[l];
-                add_job(nets[i].p, chunks_s, 8 * chunks_s, EW, layer_in(nets[i].p, l), 0, d.partial, d.partial_db, nets[i].dW[l], nets[i].db[l]);
-            }
-            static bool done_[DGM_MAX_DEVICES] = {false};
-            if (p4_lds_attr(mlp_dw4_group_kernel<2, 8, 256, 128, 1024, 512>, CfgDwE64::LDS, &done_[current_device_slot()]) != hipSuccess)
-                return fail("mlp: cannot raise the LDS limit of a plane-path kernel");
-            hipLaunchKernelGGL((mlp_dw4_group_kernel<2, 8, 256, 128, 1024, 512>), dim3(chunks_s, 2), dim3(512), CfgDwE64::LDS, st, dg);
+        LayerDw g[2];  // jobs per layer: the embedding rows' A, B (layers 5 and 0) first, then the trunk rows' A, B
+        for (int i = 0; i < 2; i++) g[i] = layer_dw(bp, nets[i].p, nets[i].w, l, G[i], Ge[i], nets[i].dW, nets[i].db, rb, rb.n_jobs + i, 2);
+        rb.n_jobs += 2 * g[0].n_jobs;
+        if (l == 0 || l == sk) {  // the embedding's rows of the gradient, with the layer's bias gradient (blockIdx.y = network)
+            for (int i = 0; i < 2; i++) dg.a[i] = g[i].emb;
+            if (launch_lds<mlp_dw4_group_kernel<2, 8, 256, 128, 1024, 512>>(dim3(bp.chunks, 2), 512, CfgDwE64::LDS, st, dg)) return 1;
         }
         if (l == 0) break;
         for (int i = 0; i < 2; i++) {  // backward data G_{l-1} = (G_l W_l) masked, into the other buffer; the trunk rows of dW_l
             const Ws& w = nets[i].w;
             Gemm4Args& a = pg.ga[i];
             a.A = G[i], a.Aexp = Ge[i], a.Bp = w.Wd3[l], a.b_inv = w.wsc_d[l], a.mask_in = w.mask[l - 1], a.C = Gn[i], a.Cexp = Gne[i];
-            Dw4Args& d = pg.da[i];
-            d.tiles_per_chunk = tpc_pair;
-            d.X = (const unsigned char*)w.Y[l - 1], d.Xexp = w.Yexp[l - 1], d.G = G[i], d.Gexp = Ge[i];
-            d.partial = w.partial_l[l], d.chunk_stride = (size_t)MLP_W * MLP_W;
-            d.partial_db = l == sk ? nullptr : w.partial_db_l[l];  // (the skip layer's bias gradient came with its embedding half)
-            if (l == sk)
-                add_job(nets[i].p, chunks_pair, 0, MLP_W, layer_in(nets[i].p, l), nets[i].p->emb_dim, d.partial, nullptr, nets[i].dW[l], nullptr);
-            else
-                add_job(nets[i].p, chunks_pair, 8 * chunks_pair, MLP_W, layer_in(nets[i].p, l), 0, d.partial, d.partial_db, nets[i].dW[l], nets[i].db[l]);
+            pg.da[i] = g[i].trunk;
         }
         // this launch's reduce role: the jobs the previous iteration queued (their tiles are complete); the final launch skips those pieces
         pr.n_hidden = (l < 7 && n_hidden > 0) ? n_hidden : 0;
@@ -1334,31 +1300,16 @@ int backward_planes_group(const GroupNet* nets, int N, const int n_wg, hipStream
                 jb.first_block = pr.n_hidden;
                 pr.job[i] = jb;
             }
-        for (int i = 0; i < 2; i++) hidden_slot[i] = n_pending - 2 + i;
+        for (int i = 0; i < 2; i++) hidden_slot[i] = rb.n_jobs - 2 + i;
         dgm::prof_begin(DGM_STAGE_MLP_BWD_PAIR, st, 2);  // (counts as the two layer passes it carries)
-        {
-            static bool done_[DGM_MAX_DEVICES] = {false};
-            constexpr int LDS_PAIR = CfgBwdC::LDS > CfgDw::LDS ? CfgBwdC::LDS : CfgDw::LDS;
-            if (p4_lds_attr(mlp_bwd_pair_group_kernel<true>, LDS_PAIR, &done_[current_device_slot()]) != hipSuccess)
-                return fail("mlp: cannot raise the LDS limit of mlp_bwd_pair_group_kernel");
-            static_assert(LDS_PAIR >= 2 * RDW_LDS_FLOATS * 4 + 16, "the reduce role's two pieces and its ticket slot live in the launch's LDS");
-            hipLaunchKernelGGL(mlp_bwd_pair_group_kernel<true>, dim3(4 * n_wg), dim3(512), LDS_PAIR, st, pg, n_wg, cpw, n_dw, pr);
-        }
+        static_assert(LDS_PAIR >= 2 * RDW_LDS_FLOATS * 4 + 16, "the reduce role's two pieces and its ticket slot live in the launch's LDS");
+        if (launch_lds<mlp_bwd_pair_group_kernel<true>>(4 * n_wg, 512, LDS_PAIR, st, pg, n_wg, cpw, bp.n_dw, pr)) return 1;
         dgm::prof_end(DGM_STAGE_MLP_BWD_PAIR, st);
-        for (int i = 0; i < 2; i++) {
-            unsigned char* t = G[i];
-            G[i] = Gn[i], Gn[i] = t;
-            int* te = Ge[i];
-            Ge[i] = Gne[i], Gne[i] = te;
-        }
+        for (int i = 0; i < 2; i++) std::swap(G[i], Gn[i]), std::swap(Ge[i], Gne[i]);
     }
-    rb.n_jobs = n_pending;  // 18: what two backward_planes() passes queue, job for job
-    for (int i = 0; i < 2; i++) {
-        ReduceDwBatch::Heads& h = rb.heads[i];
-        h.chunks = chunks_s, h.bchunks = nt, h.nout = nets[i].p->n_out;
-        h.partial_W = nets[i].w.partial_h, h.partial_b = nets[i].w.partial_hb, h.dW = nets[i].dWh, h.db = nets[i].dbh;
-    }
-    hipLaunchKernelGGL(mlp_reduce_dw_all_kernel, dim3(rb_blocks, rb.n_jobs + 2), dim3(256), 0, st, rb);
+    // rb.n_jobs = 18: what two backward_planes() passes queue, job for job
+    for (int i = 0; i < 2; i++) set_heads(rb.heads[i], bp, nets[i].p, nets[i].w, nets[i].dWh, nets[i].dbh);
+    launch_reduce_all(rb, 2, st);
     {   // the time columns of dW_0 / dW_skip: db (x) t_emb; and dL/dt_emb
         FoldGradGroupArgs fg;
         int tmax = 0;
@@ -1374,9 +1325,7 @@ int backward_planes_group(const GroupNet* nets, int N, const int n_wg, hipStream
         }
         hipLaunchKernelGGL(mlp_fold_grad_group_kernel, dim3(any_dt ? 3 : 2, tmax, 2), dim3(256), 0, st, fg);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(hipGetErrorString(e));
-    return 0;
+    return launch_status();
 }
 }  // namespace
 
@@ -1422,8 +1371,8 @@ __global__ void p4_probe_fill_kernel(unsigned* __restrict__ p, size_t n, unsigne
 }  // namespace
 int dgm_p4_probe(int N, int kind, int iters, int zero, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    const P4Plan pl = p4_plan(N);
-    const int nt = pl.ntiles, gx = nt < num_cus() ? nt : num_cus();
+    const BwdPlan bp = bwd_plan(N, false);
+    const int nt = bp.nt, gx = bp.gx;
     static unsigned char *A = nullptr, *C = nullptr, *G = nullptr;
     static int* ex = nullptr;
     static uint4* Bp = nullptr;
@@ -1458,34 +1407,27 @@ int dgm_p4_probe(int N, int kind, int iters, int zero, void* stream) {
     a.exps_limit = 512;
     a.ntiles = nt, a.M = N, a.A = kind == 0 ? A : G, a.Aexp = ex, a.Bp = Bp, a.b_inv = binv, a.bias = bias, a.mask_in = mask,
     a.mask_out = mask + (size_t)0, a.C = C, a.Cexp = ex + nt;
-    Dw4Args d;
-    memset(&d, 0, sizeof(d));
-    d.ntiles = nt, d.tiles_per_chunk = pl.tiles_per_chunk, d.X = A, d.Xexp = ex + 2 * nt, d.G = G, d.Gexp = ex + 3 * nt, d.partial = partial,
-    d.chunk_stride = (size_t)256 * 256, d.partial_db = pdb;
-    int n_dw = p4_pair_split(nt, gx);
-    if (n_dw > pl.chunks) n_dw = pl.chunks;
+    const Dw4Args d = dw4_args(nt, bp.tiles_per_chunk, A, ex + 2 * nt, G, ex + 3 * nt, partial, (size_t)256 * 256, pdb);
     Gemm5Args a5;
     memset(&a5, 0, sizeof(a5));
     a5.exps_limit = 512, a5.ntiles = nt, a5.M = N, a5.A = (kind == 4) ? A : G, a5.Aexp = ex, a5.Bp = Bp, a5.b_inv = binv, a5.bias = bias;
     a5.mask_in = mask, a5.mask_out = mask, a5.C = C, a5.Cexp = ex + nt;
     for (int it = 0; it < iters; it++) {
         if (kind == 4) {  // round 6: the one-wave-per-SIMD forms
-            P5_LAUNCH((mlp_gemm5_kernel<0, 0>), Cfg5Fwd::LDS, gx, st, a5)
+            if (launch_lds<mlp_gemm5_kernel<0, 0>>(gx, 256, Cfg5Fwd::LDS, st, a5)) return 1;
         } else if (kind == 5) {
-            P5_LAUNCH((mlp_gemm5_kernel<0, 1>), Cfg5Bwd::LDS, gx, st, a5)
+            if (launch_lds<mlp_gemm5_kernel<0, 1>>(gx, 256, Cfg5Bwd::LDS, st, a5)) return 1;
         } else if (kind == 0) {
-            P4_LAUNCH((mlp_gemm4_kernel<16, 1024, 512, 0, false, 8>), CfgFwd::LDS, gx, st, a)
+            if (launch_lds<mlp_gemm4_kernel<16, 1024, 512, 0, false, 8>>(gx, 512, CfgFwd::LDS, st, a)) return 1;
         } else if (kind == 3) {
-            P4_LAUNCH((mlp_gemm4_kernel<16, 1024, 512, 1, false, 8>), CfgBwd::LDS, gx, st, a)
+            if (launch_lds<mlp_gemm4_kernel<16, 1024, 512, 1, false, 8>>(gx, 512, CfgBwd::LDS, st, a)) return 1;
         } else if (kind == 1) {
-            P4_LAUNCH((mlp_dw4_kernel<8, 8, 1024, 512, 1024, 512>), CfgDw::LDS, pl.chunks, st, d)
+            if (launch_lds<mlp_dw4_kernel<8, 8, 1024, 512, 1024, 512>>(bp.chunks, 512, CfgDw::LDS, st, d)) return 1;
         } else {
-            if (n_dw <= 0) return fail("p4_probe: no pair split at this size");
-            static bool done_[DGM_MAX_DEVICES] = {false};
-            constexpr int LDS_PAIR = CfgBwd::LDS > CfgDw::LDS ? CfgBwd::LDS : CfgDw::LDS;
-            if (p4_lds_attr(mlp_bwd_pair_kernel<false>, LDS_PAIR, &done_[current_device_slot()]) != hipSuccess) return fail("p4_probe: LDS attribute");
+            if (bp.n_dw <= 0) return fail("p4_probe: no pair split at this size");
+            constexpr int LDS_PROBE = CfgBwd::LDS > CfgDw::LDS ? CfgBwd::LDS : CfgDw::LDS;
             Dw4Args dp = d;
-            dp.tiles_per_chunk = (nt + n_dw - 1) / n_dw;
+            dp.tiles_per_chunk = bp.tpc_pair;
 #ifdef P4_XCD_REDUCE
             {
                 static unsigned* xs = nullptr;
@@ -1495,17 +1437,13 @@ int dgm_p4_probe(int N, int kind, int iters, int zero, void* stream) {
                     if (hipMalloc((void**)&xs, 8 * 128) != hipSuccess || hipMalloc((void**)&xp, (size_t)8 * 65536 * 4) != hipSuccess) return fail("p4_probe: hipMalloc");
                     (void)hipMemsetAsync(xs, 0, 8 * 128, st);
                 }
-                dp.xsync = getenv("DGM_P4_XCD_OFF") ? nullptr : xs, dp.xpartial = xp, dp.xgen = gen++, dp.xchunks = (nt + dp.tiles_per_chunk - 1) / dp.tiles_per_chunk;
+                dp.xsync = g_env.xcd_off ? nullptr : xs, dp.xpartial = xp, dp.xgen = gen++, dp.xchunks = bp.chunks_pair;
             }
 #endif
-            const int grid = n_dw + (gx - n_dw > 0 ? gx - n_dw : 1);
-            const int chunked = (grid - n_dw == n_dw && (n_dw % 8) == 0) ? 1 : 0;
-            hipLaunchKernelGGL(mlp_bwd_pair_kernel<false>, dim3(grid), dim3(512), LDS_PAIR, st, a, dp, n_dw, chunked);
+            if (launch_lds<mlp_bwd_pair_kernel<false>>(bp.pair_grid, 512, LDS_PROBE, st, a, dp, bp.n_dw, bp.chunked)) return 1;
         }
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(hipGetErrorString(e));
-    return 0;
+    return launch_status();
 }
 #endif
 
@@ -1545,7 +1483,9 @@ int dgm_mlp_forward_add(const dgm_mlp_params* p, int N, const float* x, const fl
     const int mode = g_gemm_mode;
     const bool fold = (mode == 3 || mode == 5) && temb_stride == 0;
     remember_ws_mode(workspace, mode + (fold ? 16 : 0));
-    if (mode >= 3) return forward_planes(p, N, x, temb, temb_stride, w, out, st, fold, fold && mode == 5, x_add, x_add_stride);
+    if (mode >= 3)
+        return fold ? forward_folded(p, N, x, temb, w, out, st, mode == 5, x_add, x_add_stride)
+                    : forward_per_row(p, N, x, temb, temb_stride, w, out, st, x_add, x_add_stride);
     // ---- native fp32 MFMA
     for (int l = 0; l < 8; l++) {
         const int Kp = layer_kp(p, l);
@@ -1570,9 +1510,7 @@ int dgm_mlp_forward_add(const dgm_mlp_params* p, int N, const float* x, const fl
     }
     hipLaunchKernelGGL(mlp_rows_small_kernel, dim3((N * 4 + 255) / 256), dim3(256), 0, st, N, p->n_out, w.Y[7], p->Wh, 1,
                        MLP_W, p->bh, out, p->n_out, 0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(hipGetErrorString(e));
-    return 0;
+    return launch_status();
 }
 
 int dgm_mlp_backward(const dgm_mlp_params* p, int N, const float* dOut, int temb_stride, char* workspace, float* const* dW,
@@ -1600,7 +1538,8 @@ int dgm_mlp_backward_dx(const dgm_mlp_params* p, int N, const float* dOut, int t
     Ws w = carve(workspace, N);
     if (mode >= 3) {
         const bool fold = (mode == 3 || mode == 5) && temb_stride == 0;
-        return backward_planes(p, N, dOut, temb_stride, w, dW, db, dWh, dbh, dtemb, st, fold, fold && mode == 5, x, dX);
+        return fold ? backward_planes<true>(p, N, dOut, temb_stride, w, dW, db, dWh, dbh, dtemb, st, mode == 5, x, dX)
+                    : backward_planes<false>(p, N, dOut, temb_stride, w, dW, db, dWh, dbh, dtemb, st, false, x, dX);
     }
     // ---- native fp32 MFMA
     const int chunks = (N + DW_ROWS - 1) / DW_ROWS;
@@ -1648,9 +1587,7 @@ int dgm_mlp_backward_dx(const dgm_mlp_params* p, int N, const float* dOut, int t
     if (!per_row_t && dtemb != nullptr)
         hipLaunchKernelGGL(mlp_dtemb_bcast_kernel, dim3(p->t_dim), dim3(256), 0, st, p->t_dim, db[0], p->W[0], layer_in(p, 0),
                            db[p->skip_layer], p->W[p->skip_layer], layer_in(p, p->skip_layer), dtemb);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(hipGetErrorString(e));
-    return 0;
+    return launch_status();
 }
 
 int dgm_mlp_backward_group(const dgm_mlp_backward_job* a, const dgm_mlp_backward_job* b, int N, int temb_stride, void* stream) {
@@ -1663,7 +1600,8 @@ int dgm_mlp_backward_group(const dgm_mlp_backward_job* a, const dgm_mlp_backward
     if (a->workspace == b->workspace) return fail("mlp_backward_group: the two networks need workspaces of their own");
     const int mode = g_gemm_mode;
     const int fa = recall_ws_mode(a->workspace), fb = recall_ws_mode(b->workspace);
-    const int n_wg = p4_group_split(N);
+    const BwdPlan bp = bwd_plan(N, true);
+    const int n_wg = group_split(bp);
     const bool grouped = n_wg > 0 && mode == 3 && temb_stride == 0 && fa == (3 | 16) && fb == (3 | 16) &&
                          a->params->emb_dim == b->params->emb_dim;
     if (!grouped) {  // two ordinary passes back to back: what the caller would have run (and every check of theirs)
@@ -1679,7 +1617,7 @@ int dgm_mlp_backward_group(const dgm_mlp_backward_job* a, const dgm_mlp_backward
         nets[i].p = j->params, nets[i].dOut = j->dOut, nets[i].w = carve(j->workspace, N);
         nets[i].dW = j->dW, nets[i].db = j->db, nets[i].dWh = j->dWh, nets[i].dbh = j->dbh, nets[i].dtemb = j->dtemb;
     }
-    return backward_planes_group(nets, N, n_wg, (hipStream_t)stream);
+    return backward_planes_group(nets, N, bp, n_wg, (hipStream_t)stream);
 }
 
 int dgm_timenet_forward(const float* t, int n_freq, const float* W1, const float* b1, int hidden, const float* W2,
@@ -1689,9 +1627,7 @@ int dgm_timenet_forward(const float* t, int n_freq, const float* W1, const float
         return fail("timenet_forward: unsupported size (2 n_freq + 1 <= 64, hidden <= 1024, n_out <= 64)");
     hipLaunchKernelGGL(mlp_timenet_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, t, n_freq, W1, b1, hidden, W2, b2,
                        n_out, save, out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(hipGetErrorString(e));
-    return 0;
+    return launch_status();
 }
 
 int dgm_timenet_backward(const float* d_out, int n_freq, const float* W2, int hidden, int n_out, const float* save,
@@ -1701,9 +1637,7 @@ int dgm_timenet_backward(const float* d_out, int n_freq, const float* W2, int hi
         return fail("timenet_backward: unsupported size");
     hipLaunchKernelGGL(mlp_timenet_bwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, d_out, n_freq, W2, hidden, n_out,
                        save, dW1, db1, dW2, db2);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(hipGetErrorString(e));
-    return 0;
+    return launch_status();
 }
 
 }  // extern "C"

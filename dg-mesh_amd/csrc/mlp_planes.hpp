@@ -255,7 +255,7 @@ __device__ __forceinline__ void embed4_tile(const int N, const int tile, const f
         }
     }
     // x, the time embedding, the zero padding: 3 + (EW - 63) columns per row (EW = 64: no time columns -- one time value per call
-    // is folded into the biases, mlp_prep4c_kernel -- just the zero column 63)
+    // is folded into the biases, prep4c_block -- just the zero column 63)
     const int rest = 3 + EW - 63;
     for (int i = tid; i < 32 * rest; i += 256) {
         const int rl = i / rest, j = i - rest * rl, r = r0 + rl;
@@ -425,10 +425,6 @@ __device__ __forceinline__ void prep4c_block(const Prep4cBatch& b, const int bx,
     }
 }
 
-__global__ void __launch_bounds__(256)
-mlp_prep4c_kernel(const Prep4cBatch b) {
-    prep4c_block(b, (int)blockIdx.x, (int)blockIdx.y);
-}
 // The embedding planes and the weight preparation in ONE launch (round 6's forms: neither needs anything of the other): the first
 // n_prep = 16 x jobs workgroups prepare the weights (dispatched first: their scattered row reads are the longer chain), the rest take
 // one 32-row tile of the embedding each.  (Two launches: 13.1 + 10.2 us.)
@@ -560,7 +556,7 @@ struct Gemm4Cfg {
 // All vector-memory traffic of a step is one burst with a full step of slack, so neither HBM latency nor a momentary
 // shortage of bandwidth stalls the matrix cores; loads and stores may complete in any order (the counter is only ever
 // waited down to zero).
-// COLSC: a.b_inv points to one inverse scale per output column (mlp_prep4c_kernel) instead of one per matrix, a.bias (EPI 0) is
+// COLSC: a.b_inv points to one inverse scale per output column (prep4c_block) instead of one per matrix, a.bias (EPI 0) is
 // pre-scaled; the epilogue multiplies output column c by b_inv[c] behind the ReLU / the mask (powers of two: exact).
 template <int KS, int ROWB, int PLANEB, int EPI, bool DUAL, int NCW, bool COLSC = false>
 __device__ __forceinline__ void gemm4_body(const Gemm4Args& a, const int bx, const int G, unsigned char* smem, const int tiles_in = -1) {

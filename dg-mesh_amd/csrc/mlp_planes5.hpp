@@ -8,7 +8,7 @@
 // at K = 256, 320 at K = 320), which is also what lets the skip layer run as ONE K = 320 GEMM:
 //   KS2 = 4: four more K steps over the 64-column embedding planes [x, PE(x), 0] (a second DMA stream into its own LDS rows) run
 //            FIRST; the accumulators are then rescaled by 2^(e_trunk - e_emb) (exact) and the 16 trunk steps follow.  The time
-//            embedding is one row per call (R/train.py:158) and sits in the bias (mlp_prep4c_kernel's fold jobs) -- the 102 MB fp32 `Cin`
+//            embedding is one row per call (R/train.py:158) and sits in the bias (prep4c_block's fold jobs) -- the 102 MB fp32 `Cin`
 //            round trip of rounds 2-5 is gone.
 // Two independent accumulator chains alternate MFMA by MFMA, so the matrix pipe needs no second wave to stay busy; everything
 // else (E1 / E2 epilogue slices between the MFMAs, one vmcnt(0) per tile step at the mid barrier, three A buffers filled by
@@ -40,7 +40,7 @@ struct Gemm5Args {
     const unsigned char* A2;    // KS2 > 0: embedding planes [Np][2][64]
     const int* A2exp;           // [ntiles]
     const uint4* Bp;            // weight planes, K steps in execution order: KS2 embedding steps, then the 16 trunk steps
-    const float* b_inv;         // [256] inverse column scales (mlp_prep4c_kernel); bias is pre-scaled
+    const float* b_inv;         // [256] inverse column scales (prep4c_block); bias is pre-scaled
     const float* bias;          // [256] (EPI 0)
     const unsigned* mask_in;    // EPI 1
     unsigned* mask_out;         // EPI 0
@@ -48,7 +48,7 @@ struct Gemm5Args {
     int* Cexp;                  // [ntiles]
     int exps_limit;             // tiles of a workgroup whose input exponents come from its LDS table; later ones from HBM
     // EPI 2 (the last trunk layer with the output heads riding along): out[row][o] = Y[row] . Wh[o] + bh[o], o < h_nout <= 16
-    const uint4* hBp;           // heads' weight planes [16 K steps][2 halves | 2 planes][32 columns] (mlp_prep4c_kernel, ncols = 32)
+    const uint4* hBp;           // heads' weight planes [16 K steps][2 halves | 2 planes][32 columns] (prep4c_block, ncols = 32)
     const float* h_inv;         // [h_nout] inverse column scales of hBp
     const float* h_bias;        // [h_nout]
     float* h_out;               // [M][h_nout] fp32
@@ -485,7 +485,7 @@ mlp_gemm5_kernel(const Gemm5Args a) {
 // With ONE time value per call (R/train.py:158: fid expanded over the Gaussians) the time columns of the two layers that consume
 // the embedding contribute the same vector to every row: beff[j] = b[j] + sum_t W[j][63 + t] t_emb[t]   (R/utils/time_utils.py:
 // 104-129: h = cat([x_emb, t_emb]) -> linear[0]; the skip re-injection feeds linear[5] the same way).  The fold itself happens where
-// the two layers' biases are pre-scaled (mlp_prep4c_kernel, mlp_planes.hpp: `fold` jobs); first version: a launch of its own.
+// the two layers' biases are pre-scaled (prep4c_block, mlp_planes.hpp: `fold` jobs); first version: a launch of its own.
 
 // The adjoint of the fold (one launch, after the reduction has produced db; grid (3 or 2, T)).  (Tried: the same work inside
 // mlp_reduce_dw_all_kernel -- its bias-reducing workgroups writing the time columns, the last of them to arrive dL/dt_emb -- saves this

@@ -275,9 +275,11 @@ typedef struct {
 /* Arithmetic of the trunk GEMMs.  3 (default): "f16x3p" -- every fp32 operand scaled by a power of two and split into two binary16
  * numbers, three partial products accumulated in fp32 on the f16 matrix cores, on plane-format activations: every activation /
  * gradient tensor lives in HBM as its two binary16 planes with one power-of-two exponent per 32-row tile, split once by the kernel
- * that produces it.  1: native fp32 MFMA.  Both are fp32 GEMMs to rounding.  (0, "bf16x6", and 2, "f16x3" on fp32 rows, were
- * retired in rounds 4 / 5 and are ignored.)  Returns the previous mode; any other value only queries.  Process-wide; the initial
- * value comes from the environment variable DGM_MLP_GEMM=f16x3p|f32.  A forward and its backward must run in the same mode. */
+ * that produces it.  1: native fp32 MFMA.  Both are fp32 GEMMs to rounding.  4 ("f16x3p8") and 5 ("f16x3p5") are mode 3's
+ * arithmetic on other kernel forms, kept selectable as its A/B partners: 4 runs the forms of a time input per row for every call,
+ * 5 every 256-wide layer GEMM with one wave per SIMD.  (0, "bf16x6", and 2, "f16x3" on fp32 rows, were retired in rounds 4 / 5 and
+ * are ignored.)  Returns the previous mode; any other value only queries.  Process-wide; the initial value comes from the
+ * environment variable DGM_MLP_GEMM=f16x3p|f16x3p8|f16x3p5|f32.  A forward and its backward must run in the same mode. */
 int dgm_mlp_set_gemm(int mode);
 
 /* Where a grouped backward pass (dgm_mlp_backward_group) sums the weight-gradient partial tiles of its hidden layers: `pieces` of
