@@ -92,8 +92,9 @@ class _TrunkNet(nn.Module):
 
     def _time_rows(self, t):
         """(t_emb, broadcast): t identical on every row (expanded view, R/train.py:158) -> evaluate the time branch
-        on ONE row and broadcast it."""
-        if t.dim() == 2 and t.shape[0] > 1 and t.stride(0) == 0:
+        on ONE row and broadcast it.  A batch of one row is that case too (its stride says nothing): it used to count as a time
+        value per row, for which the fused trunk has no dL/dx."""
+        if t.dim() == 2 and (t.shape[0] == 1 or (t.shape[0] > 1 and t.stride(0) == 0)):
             if self.trunk_impl == "hip" and self.is_blender and t.is_cuda and t.shape[1] == 1:
                 from . import mlp_hip
                 return mlp_hip.time_row(self, t[:1]), True  # one small kernel instead of ~45 one-element ones

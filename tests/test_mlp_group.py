@@ -81,10 +81,12 @@ def _names(a, b):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("N", [33_000, 60_000, 100_003])
+@pytest.mark.parametrize("N", [32_737, 32_768, 32_769, 33_000, 60_000, 100_003])
 def test_grouped_pass_equals_two_separate_passes(N):
-    """N = 33 000: the smallest paired size, a ragged last tile, 1 032 tiles in 115 chunks of 9 over 64 workgroups of two chunks: the
-    last six workgroups have one chunk or none; N = 60 000: 1 875 tiles in 125 chunks of 15, one workgroup with one chunk, one
+    """N = 32 737 and 32 768 (256 CUs; tests/_mlp_plan.py derives them): the smallest paired sizes, 1 024 tiles in 128 chunks of 8,
+    every workgroup two full chunks, the last tile one row or full; N = 32 769: 1 025 tiles in 114 chunks of 9, a one-row last tile,
+    seven workgroups without a chunk; N = 33 000: a ragged last tile, 1 032 tiles in 115 chunks of 9 over 64 workgroups of two chunks:
+    the last six workgroups have one chunk or none; N = 60 000: 1 875 tiles in 125 chunks of 15, one workgroup with one chunk, one
     idle; N = 100 003: the bench's size with a ragged tile."""
     a, b, x, w, (og, gg), (os_, gs) = _case(N)
     for u, v in zip(og, os_):
@@ -144,7 +146,7 @@ def test_grouped_pass_is_an_fp32_pass(N):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("N", [33_000, 60_000])
+@pytest.mark.parametrize("N", [32_737, 32_769, 33_000, 60_000])
 def test_grouped_pass_reads_only_what_it_wrote(N):
     """The pattern of test_mlp.test_backward_reads_only_what_the_pass_wrote on the grouped pass: the allocator's cached blocks are
     filled with NaN bit patterns before the pass -- partial tiles of the workgroups without tiles do not exist and must not be
@@ -211,12 +213,12 @@ def _raw_backward(nets, x, temb, temb_stride, dOut, grouped):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("per_row", [False, True])
-def test_fallback_is_bit_identical_to_two_passes(per_row):
-    """N = 4 096 is below the paired launches' size; a time input per row has no folded form: either way the grouped entry point
-    runs two ordinary passes and returns their bits."""
+@pytest.mark.parametrize("N,per_row", [pytest.param(4096, False, id="False"), pytest.param(4096, True, id="True"),
+                                       pytest.param(32_736, False, id="32736")])
+def test_fallback_is_bit_identical_to_two_passes(N, per_row):
+    """N = 4 096 is below the paired launches' size, N = 32 736 the largest size below it (256 CUs: 1 023 tiles, four per chunk); a
+    time input per row has no folded form: either way the grouped entry point runs two ordinary passes and returns their bits."""
     dev = "cuda"
-    N = 4096
     a, b = _nets()
     x, w = _inputs(N)
     gen = torch.Generator(device=dev).manual_seed(3)
